@@ -14,6 +14,11 @@ A step = one batch of B synthetic complex-float IQ samples resident in HBM
 nz = 1e6, zero-padded), c3 (xlator + 256-tap FIR /8 + FM quadrature, fused), c4 (1024-channel
 polyphase channelizer, 16384-tap prototype).
 
+A plain run sets up --config, warms up, times the K steps and prints one JSON line (value, ms_per_step, the
+dominant group's roofline from the timed steps' own events); --dump-outputs DIR also writes what the last timed
+step computed. --full adds everything that takes runs of its own: the other configs, the per-call figures, the
+spectrum ulp report and fp64-mode cost, the CPU baselines and the speed-ups against them.
+
 Launch: python bench.py [--gpus N --steps K --warmup W]. N > 1 either under torch.distributed.run
 (WORLD_SIZE must equal N) or directly: the parent then starts N rank processes itself before anything
 touches the GPU (launch_ranks) and exits with the first failing rank's status.
@@ -37,11 +42,17 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c5", choices=["c5", "c2", "c3", "c4", "c4g"])
     ap.add_argument("--log2-batch", type=int, default=28, help="IQ samples per GPU per step = 2^k (c5/c3)")
-    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline leg (1-core, all-core)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="time only --config (no C2/C3/C4 sub-objects)")
-    ap.add_argument("--no-ulp", action="store_true", help="skip the live spectrum ulp report (profiling runs: "
-                    "only the timed config's kernels run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed config also: the other single-GPU configs, the per-call figures, the live "
+                         "spectrum ulp report and fp64-mode cost, and the CPU baselines with the speed-ups against them "
+                         "(a plain run times --config only and prints its line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step of --config computed to DIR/<name>.npy "
+                         "(float32; arrays over 2^23 elements as a fixed seeded sample; at most 64 MB in all)")
+    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline leg (1-core, all-core; --full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-sub", action="store_true", help="--full without the other configs and the per-call figures")
+    ap.add_argument("--no-ulp", action="store_true", help="--full without the live spectrum ulp report and fp64-mode cost")
     ap.add_argument("--runtime", default="hip", choices=["hip", "cpu-rehearsal"],
                     help="cpu-rehearsal: the same launch / gather / timing control flow on the CPU over gloo with a "
                          "C5-shaped CPU stand-in workload (tests only; its line says so and is no measurement)")
@@ -197,7 +208,8 @@ class C5:
             m = self.fft.execute_zoom_vfo_dev(x.data_ptr(), self.frames, self.spectra.data_ptr(), z, self.ZW, self.vfo,
                                               self.ifbuf.data_ptr(), s)
             if self.tail is not None and self.with_zoom:   # the VFO output is complete on the tail stream
-                self.wfm.process_dev(self.ifbuf.data_ptr(), m, self.audio.data_ptr(), self.tail.cuda_stream)
+                self.counts = (buf, m, self.wfm.process_dev(self.ifbuf.data_ptr(), m, self.audio.data_ptr(),
+                                                            self.tail.cuda_stream))
                 return
         else:
             if self.with_zoom:
@@ -206,7 +218,16 @@ class C5:
             else:   # (A/B only: BENCH_C5_ZOOM=0 drops the waterfall rows)
                 timed_call(lambda: self.fft.execute_dev(x.data_ptr(), self.N, self.frames, self.spectra.data_ptr(), s))
             m = self.vfo.process_dev(x.data_ptr(), self.B, self.ifbuf.data_ptr(), s)
-        self.wfm.process_dev(self.ifbuf.data_ptr(), m, self.audio.data_ptr(), s)
+        self.counts = (buf, m, self.wfm.process_dev(self.ifbuf.data_ptr(), m, self.audio.data_ptr(), s))
+
+    def outputs(self):
+        """What the last step handed its caller: the dB rows, the waterfall rows it wrote, the VFO's
+        complex output and the stereo audio (both interleaved, the counts the blocks returned)."""
+        buf, m, na = self.counts
+        out = {"spectra": self.spectra, "vfo_iq": self.ifbuf[:2 * m], "audio_stereo": self.audio[:2 * na]}
+        if self.with_zoom:
+            out["waterfall_rows"] = self.zoom[buf][:self.zoom_count]
+        return out
 
     def group_ms(self, steps):
         """The dominant group's mean time over the timed steps from the library's own HIP events
@@ -236,6 +257,9 @@ class C2:
     def dominant(self, x, s):
         self.fft.execute_dev(x.data_ptr(), self.NZ, self.frames, self.spectra.data_ptr(), s)
 
+    def outputs(self):
+        return {"spectra": self.spectra}
+
     def rest(self, x, s):
         pass
 
@@ -255,7 +279,10 @@ class C3:
         self.kernel_name = "fir_mfma_kernel<4,XL,QUAD,HALF,D=8> (xlator + 256-tap FIR /8 on f32 MFMA + quadrature; half the phases' span in LDS at a time, 4 workgroups per CU; D a compile-time constant)"
 
     def dominant(self, x, s):
-        self.ddc.process_dev(x.data_ptr(), self.B, self.out.data_ptr(), s)
+        self.count = self.ddc.process_dev(x.data_ptr(), self.B, self.out.data_ptr(), s)
+
+    def outputs(self):
+        return {"fm_demod": self.out[:self.count]}
 
     def rest(self, x, s):
         pass
@@ -289,7 +316,10 @@ class C4:
                         "so the 576-flop DFT-GEMM form would be compute-bound where the FFT form is HBM-bound"}
 
     def dominant(self, x, s):
-        self.ch.process_dev(x.data_ptr(), self.B, self.out.data_ptr(), s)
+        self.count = self.ch.process_dev(x.data_ptr(), self.B, self.out.data_ptr(), s)
+
+    def outputs(self):
+        return {"channels_iq": self.out[:2 * self.count]}   # complex [frame][channel], interleaved
 
     def rest(self, x, s):
         pass
@@ -461,6 +491,39 @@ def traffic_per_sample(config):
         except (OSError, KeyError, ValueError):
             continue
     return None, None
+
+
+DUMP_WHOLE = 1 << 23          # --dump-outputs: arrays up to this many elements are written whole,
+DUMP_SAMPLE = 1 << 21         # larger ones as this many elements at fixed, seeded positions
+DUMP_MAX_BYTES = 64 * 10**6   # of float32 in all
+DUMP_SEED = 0xD0E5
+
+
+def dump_plan(sizes):
+    """{name: None (the whole array) or sorted int64 positions into it} for output arrays of
+    `sizes[name]` elements. The positions depend only on the array's length, so two builds run
+    with the same arguments write the same elements. Should the arrays written whole not fit in
+    DUMP_MAX_BYTES (a --log2-batch above the default), the whole/sample sizes halve until they do."""
+    whole = DUMP_WHOLE
+
+    def kept(c):
+        return c if c <= whole else min(DUMP_SAMPLE, whole)
+    while 4 * sum(kept(c) for c in sizes.values()) > DUMP_MAX_BYTES:
+        whole //= 2
+    return {n: None if c <= whole else np.sort(np.random.default_rng([DUMP_SEED, c]).integers(0, c, kept(c)))
+            for n, c in sizes.items()}
+
+
+def dump_outputs(wl, path):
+    """--dump-outputs: the workload's outputs() of its last step as <path>/<name>.npy (float32)."""
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    outs = wl.outputs()
+    for name, pos in dump_plan({n: t.numel() for n, t in outs.items()}).items():
+        t = outs[name]
+        if pos is not None:
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 WORKLOADS = {"c5": "C5 per-GPU slice: 64k BH7 FFT+log-mag (back-to-back) + 2048-column waterfall zoom + RxVFO "
@@ -789,6 +852,8 @@ def rehearsal_main(a):
     """`--runtime cpu-rehearsal`: this rank's run_config over gloo with the CPU stand-in; rank 0
     prints the line (marked as a rehearsal, with the gather report and this rank's last rows'
     checksums so a test can check what rank 0 received)."""
+    if a.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs needs --runtime hip (the rehearsal computes nothing to compare)")
     shard = StreamShard(backend="gloo")
     world, rank = shard.world, shard.rank
     B, elapsed, kern_ms, wl = run_config(a.config, a, shard, None, "compute", rt=CpuRehearsalRuntime(),
@@ -822,11 +887,15 @@ def main():
     stream = torch.cuda.current_stream()
     B, elapsed, kern_ms, wl = run_config(a.config, a, shard, dev, stream)
     head = config_result(a.config, a, world, B, elapsed, kern_ms, wl)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(wl, a.dump_outputs)
     del wl
+    # everything below the timed config is --full only; --no-sub / --no-ulp / --no-cpu drop parts of it
+    sub, ulp, cpu = (a.full and not off for off in (a.no_sub, a.no_ulp, a.no_cpu))
     # the other single-GPU configs of BASELINE.json, timed the same way in the same run (N = 1 only:
     # C2 and C3 carry the north_star's >= 10x / >= 40% targets, C4 the channelizer)
     subs = {}
-    if world == 1 and not a.no_sub:
+    if world == 1 and sub:
         for c in ("c2", "c3", "c4", "c4g", "c5"):
             if c == a.config:
                 continue
@@ -850,10 +919,10 @@ def main():
             out["roofline_flops"] = head["roofline_flops"]
         if "gather" in head:
             out["gather"] = head["gather"]
-        if not a.no_ulp:
+        if ulp:
             out["spectrum_ulp"] = spectrum_ulp_report(dev)
             out["spectrum_f64_mode_cost"] = spectrum_f64_cost(dev, stream)
-        if world == 1 and not a.no_cpu:
+        if world == 1 and cpu:
             out["cpu_baseline"] = cpu_baseline("c4" if a.config == "c4g" else a.config, a.cpu_seconds, head["bytes_per_sample"])
             out["speedup_vs_cpu_all_cores"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
             out["speedup_vs_cpu_all_affinity_linear"] = round(out["value"] / out["cpu_baseline"]["value_all_affinity_cpus_linear"], 2)
@@ -874,7 +943,7 @@ def main():
                     r["speedup_vs_whole_host_bound"] = round(r["value"] / r["cpu_baseline"]["value_whole_host_dram_bound"], 2)
         if subs:
             out["configs"] = subs
-        if world == 1 and a.config == "c5" and not a.no_sub:
+        if world == 1 and a.config == "c5" and sub:
             out["per_call"] = per_call_c5(dev, stream)
         print(json.dumps(out), flush=True)
     shard.close()

@@ -41,7 +41,9 @@ def _worker(rank, world, port, q):
     # every rank's last published rows, for rank 0's independent check
     last = shard.all_gather_tensor(wl.history[-1])
     if rank == 0:
-        q.put((r, [last[i].clone() for i in range(world)], elapsed, kern_ms))
+        # as numpy arrays, pickled by value: a torch tensor crosses the queue as a file descriptor that the
+        # parent has to fetch from this process, which may have exited by then
+        q.put((r, [last[i].numpy().copy() for i in range(world)], elapsed, kern_ms))
     shard.close()
 
 
@@ -54,6 +56,7 @@ def test_run_config_world2_gloo():
     for p in ps:
         p.start()
     r, last, elapsed, kern_ms = q.get(timeout=180)
+    last = [torch.from_numpy(v) for v in last]
     for p in ps:
         p.join(timeout=120)
         assert p.exitcode == 0

@@ -45,11 +45,11 @@ def summarise(out, tag, cfg, pattern=None):
     return reduce_rows(cfg, rows, line)
 
 
-BENCH_ORDER = ["c5", "c2", "c3", "c4", "c4g"]   # bench.py main(): the head config, then the others in this order
+BENCH_ORDER = ["c5", "c2", "c3", "c4", "c4g"]   # bench.py --full: the head config, then the others in this order
 
 
 def summarise_combined(out, tag):
-    """`benchprof` step: ONE default bench process under rocprofv3; every config's group dispatches are
+    """`benchprof` step: ONE `bench.py --full` process under rocprofv3; every config's group dispatches are
     taken from the window between its first dispatch and the next config's first dispatch (the live
     ulp report, the fp64-mode cost and the per-call runs come after all configs)."""
     trace = os.path.join(out, f"{tag}_benchprof", "run_kernel_trace.csv")

@@ -5,8 +5,8 @@
 #   tests   every -m gpu test (one pytest process; failures are recorded, the session goes on)
 #   corpus  spectrum ulp corpus (tools/fft_corpus.py), in-tree build + CORPUS_VARIANTS lib_<v> builds
 #   smoke   __graft_entry__.smoke()
-#   bench   the default bench line (all configs, CPU legs, per-call)   -> TAG_bench.json
-#   benchprof the default bench under rocprofv3 --kernel-trace --stats: the line and its trace from one
+#   bench   the full bench line (bench.py --full: all configs, CPU legs, per-call) -> TAG_bench.json
+#   benchprof the full bench (--full) under rocprofv3 --kernel-trace --stats: the line and its trace from one
 #           process -> TAG_bench.json, TAG_benchprof/, TAG_benchprof_summary.json
 #   prof    per config in PROF_CFGS: rocprofv3 --kernel-trace --stats around `bench.py --config c
 #           --no-sub --no-cpu --no-ulp`; the same process's JSON line is kept next to the stats, and
@@ -56,11 +56,11 @@ for step in $STEPS_LIST; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${TAG}_smoke.log" 2>&1
     st smoke $? ;;
   bench)
-    timeout -k 10 700 python bench.py ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+    timeout -k 10 700 python bench.py --full ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
     st bench $? ;;
-  benchprof)   # the default bench line and its kernel trace from ONE process (prof_summary --combined)
+  benchprof)   # the full bench line and its kernel trace from ONE process (prof_summary --combined)
     prof x timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_benchprof" -o run -- \
-      python3 "$R/bench.py" ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+      python3 "$R/bench.py" --full ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
     st benchprof $?
     python tools/prof_summary.py --combined "$OUT" "$TAG" > "$OUT/${TAG}_benchprof_summary.json" 2>> "$ST"
     st benchprof_summary $? ;;
