@@ -103,7 +103,10 @@ static int fe_update_fft(sdrgpu_frontend* f) {
     if (f->fft) sdrgpu_fft_destroy(f->fft);
     f->fft = nullptr;
     SDRGPU_CHECK(sdrgpu_fft_create(&f->fft, f->device, f->fftSize, nz, f->window));
-    SDRGPU_CHECK(fft_set_onepass(f->fft, 0));   // per-block calls: the two-pass launches (sdrgpu_internal.h)
+    // per-block calls hold a few frames: the 64k plan's two-pass launches, two short launches of 8 workgroups per
+    // frame, finish sooner than one launch of 2 long ones, and the split path reads the straddling frame in place
+    // (the call returns the previous mode, not a status: only a negative value is an error)
+    SDRGPU_CHECK(sdrgpu_fft_set_kernel(f->fft, 0));
     f->nz = nz;
     f->skip = skip;
     // the reshaper restarts on a path update: the next frame starts at the next sample

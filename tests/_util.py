@@ -186,7 +186,7 @@ def iq(rng, n, scale=1.0):
 
 def two_pass_fft(N, nz, window=6):
     """An FFTSpectrum on the two-pass launches of the 64k plan: the front end's transform (its plans are
-    two-pass, sdrgpu_internal.h fft_set_onepass), which its rows are checked against bit for bit."""
+    two-pass, frontend.hip fe_update_fft), which its rows are checked against bit for bit."""
     from sdrpp_amd import dsp
     keys = ("SDRGPU_TUNING", "SDRGPU_FFT_1P")
     old = {k: os.environ.get(k) for k in keys}

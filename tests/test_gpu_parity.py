@@ -1140,12 +1140,54 @@ def test_spectrum_onepass_vfo(frames_list, pre, rng, monkeypatch):
     _fused_vs_separate(frames_list, pre, rng, zoom=True)
 
 
-def test_spectrum_tail_stream_bit_identical(rng):
+@pytest.mark.parametrize("zsize,precision", [(1800, "f32"), (4096, "f32"), (2048, "f64")])
+def test_spectrum_zoom_vfo_unfused(zsize, precision, rng):
+    """execute_zoom_vfo_dev where nothing fuses (a zoom width other than N / 32, or the fp64 plan): the
+    spectrum launch group, the zoom kernel over the rows, then the whole VFO on the call's stream. Rows
+    bit-equal to execute_dev of a second plan, every zoom row bit-equal to fft_scaler's doZoom of its
+    row, and the VFO's output (after a ragged plain call: non-zero decimation phase and history) equal
+    in count and bits to a second RxVFO's process_dev."""
+    import torch
+    N, frames = 65536, 3
+    fs, off = 61.44e6, 2.5e6
+    va, vb = dsp.RxVFO(fs, 240000, 200000, off), dsp.RxVFO(fs, 240000, 200000, off)
+    x0 = iq(rng, 1000)
+    ya, yb = [va.process(x0)], [vb.process(x0)]
+    x = iq(rng, frames * N)
+    d_x = torch.from_numpy(x.view(np.float32)).cuda()
+    rows = torch.empty(frames * N, device="cuda")
+    ref = torch.empty(frames * N, device="cuda")
+    z = torch.empty(frames * zsize, device="cuda")
+    cap = frames * N // 256 + 64
+    oa = torch.empty(2 * cap, device="cuda")
+    ob = torch.empty(2 * cap, device="cuda")
+    f = dsp.FFTSpectrum(N, N, 6, precision=precision)
+    ma = f.execute_zoom_vfo_dev(d_x.data_ptr(), frames, rows.data_ptr(), z.data_ptr(), zsize, va, oa.data_ptr())
+    assert dsp.FFTSpectrum(N, N, 6, precision=precision).execute_dev(d_x.data_ptr(), N, frames, ref.data_ptr()) == frames
+    mb = vb.process_dev(d_x.data_ptr(), frames * N, ob.data_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(rows, ref)
+    r = rows.cpu().numpy().reshape(frames, N)
+    zr = z.cpu().numpy().reshape(frames, zsize)
+    for j in range(frames):
+        np.testing.assert_array_equal(zr[j], oracle.zoom(r[j], 0.0, 1.0, 1.0, zsize))
+    assert ma == mb
+    ya.append(oa[:2 * ma].cpu().numpy().view(np.complex64))
+    yb.append(ob[:2 * mb].cpu().numpy().view(np.complex64))
+    ya, yb = np.concatenate(ya), np.concatenate(yb)
+    assert len(ya) == len(yb)
+    np.testing.assert_array_equal(ya.view(np.uint64), yb.view(np.uint64))
+
+
+@pytest.mark.parametrize("kernel", ["auto", "one-pass"])
+def test_spectrum_tail_stream_bit_identical(kernel, rng):
     """sdrgpu_fft_set_tail_stream: the VFO's later stages and the zoom fold on a second stream,
     overlapping the next call's one-pass launch (their inputs double-buffered per call parity). Over
     five calls -- one-pass calls of both parities, a short call that takes the two-pass path, a zoom-less
     call -- the rows, zoom rows and the VFO output stream are bit-identical to the same calls on one
-    stream, and the VFO continues correctly on a plain process_dev call afterwards."""
+    stream, and the VFO continues correctly on a plain process_dev call afterwards. With the kernel
+    pinned to "one-pass" the 8-frame call stays on the one-pass kernel, where its tail is no big-call
+    tail: inside tail-stream mode it falls through to the same-stream sequence."""
     import torch
     N, zw = 65536, 2048
     fs, off = 61.44e6, 2.5e6
@@ -1155,6 +1197,8 @@ def test_spectrum_tail_stream_bit_identical(rng):
     res = {}
     for mode in ("one", "tail"):
         f = dsp.FFTSpectrum(N, N, 6)
+        if kernel != "auto":
+            assert f.set_kernel(kernel) == "auto"
         v = dsp.RxVFO(fs, 240000, 200000, off)
         s = torch.cuda.Stream()
         ts = torch.cuda.Stream() if mode == "tail" else None
