@@ -223,6 +223,30 @@ int sdrgpu_channelizer_create(sdrgpu_block** h, int device, int channels, const 
  * 1 = the polyphase filterbank "cast as batched MFMA GEMM" (BASELINE C4): 1024 = 32 x 32, two
  * complex 32x32 products per frame on v_mfma_f32_16x16x4_f32. M = 1024 only. */
 int sdrgpu_channelizer_set_dft(sdrgpu_block* h, int mode);
+/* IF noise reduction: the three optional blocks of the radio module between the VFO and the
+ * demodulator (decoder_modules/radio/src/radio_module.h:73-79). All C64 -> C64, out_count == count;
+ * in and out must not overlap. */
+/* noise_reduction::FMIF (noise_reduction/fm_if.h:20-77): per sample, the nuttall-windowed DFT of the
+ * last `bins` samples, the bin of largest magnitude (lowest on a tie) kept, sample bins/2 of the
+ * unnormalised back transform out. bins in [3, 32] (radio_module.h:30-35 offers 9, 15, 31, 32),
+ * checked before the device is selected. History (bins - 1 samples, zero at creation / reset /
+ * set_bins) stays on the device; results do not depend on how the stream is cut into calls. */
+#define SDRGPU_FMIF_MIN_BINS 3
+#define SDRGPU_FMIF_MAX_BINS 32
+int sdrgpu_fmif_create(sdrgpu_block** h, int device, int bins);
+int sdrgpu_fmif_set_bins(sdrgpu_block* h, int bins);          /* setBins (fm_if.h:26-34): new window, history cleared */
+int sdrgpu_fmif_window(int bins, float* out);                 /* host only: the `bins` window floats (fm_if.h:112) */
+/* noise_reduction::NoiseBlanker (noise_reduction/noise_blanker.h:12-57): serial recurrence on the
+ * running amplitude, bit-identical to the reference arithmetic; amp survives set, reset -> 1.0f */
+int sdrgpu_noise_blanker_create(sdrgpu_block** h, int device, double rate, double level);
+int sdrgpu_noise_blanker_set(sdrgpu_block* h, double rate, double level);   /* setRate / setLevel (noise_blanker.h:19-30) */
+/* noise_reduction::Squelch (noise_reduction/squelch.h:19-63): per call, level = 20 log10f(mean |x|)
+ * against `level` dB with the 1 dB hysteresis and the 10-call unmute count; decision and gated copy
+ * run on the caller's stream without a host synchronise. The count is per handle (the reference's is
+ * a function-local static shared by every squelch of the process). */
+int sdrgpu_squelch_create(sdrgpu_block** h, int device, double level);
+int sdrgpu_squelch_set_level(sdrgpu_block* h, double level);  /* setLevel (squelch.h:27-31): from the next call */
+int sdrgpu_squelch_get_muted(sdrgpu_block* h, int* muted);    /* state after the last call (synchronises) */
 
 int sdrgpu_block_process(sdrgpu_block* h, const void* in, int count, void* out);      /* host buffers */
 int sdrgpu_block_process_dev(sdrgpu_block* h, const void* in, int count, void* out, void* stream);

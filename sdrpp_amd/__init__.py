@@ -138,6 +138,14 @@ def _load():
         "sdrgpu_dc_blocker_create": (i, [pp, i, i, d]),
         "sdrgpu_am_create": (i, [pp, i, i, d, d, d, d, d, i]),
         "sdrgpu_ssb_create": (i, [pp, i, i, d, d, i, d, d, i]),
+        "sdrgpu_fmif_create": (i, [pp, i, i]),
+        "sdrgpu_fmif_set_bins": (i, [vp, i]),
+        "sdrgpu_fmif_window": (i, [i, fp]),
+        "sdrgpu_noise_blanker_create": (i, [pp, i, d, d]),
+        "sdrgpu_noise_blanker_set": (i, [vp, d, d]),
+        "sdrgpu_squelch_create": (i, [pp, i, d]),
+        "sdrgpu_squelch_set_level": (i, [vp, d]),
+        "sdrgpu_squelch_get_muted": (i, [vp, ctypes.POINTER(i)]),
         "sdrgpu_block_process": (i, [vp, vp, i, vp]),
         "sdrgpu_block_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_block_out_count": (i, [vp, i]),

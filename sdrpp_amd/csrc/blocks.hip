@@ -1719,6 +1719,11 @@ using namespace sdrgpu;
 // ================================================================== C ABI
 static int wrap(sdrgpu_block** h, Block* b, int rc) {
     if (rc < 0) { delete b; return rc; }
+    // The state written at creation (reset(): memsets / copies on the null stream) must be complete
+    // before the first call, which runs on a non-blocking stream the null stream does not order:
+    // a handle whose buffer recycled non-zero memory otherwise may start from it (seen once per
+    // process on a fresh Quadrature: y[-1] != 0).
+    if (hipDeviceSynchronize() != hipSuccess) { delete b; set_error("hipDeviceSynchronize failed at create"); return SDRGPU_EHIP; }
     *h = new sdrgpu_block{b};
     return SDRGPU_OK;
 }

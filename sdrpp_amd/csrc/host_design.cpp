@@ -77,6 +77,54 @@ int create_window(int type, float* buffer, int size, int centered) {
     return SDRGPU_OK;
 }
 
+// noise_reduction::FMIF's window (fm_if.h:112): fftWin[i] = (float)window::nuttall(i, bins - 1)
+int fmif_window(int bins, float* out) {
+    if (bins < SDRGPU_FMIF_MIN_BINS || bins > SDRGPU_FMIF_MAX_BINS || !out) {
+        set_error("fmif: bins %d outside [%d, %d] (or null buffer)", bins, SDRGPU_FMIF_MIN_BINS, SDRGPU_FMIF_MAX_BINS);
+        return SDRGPU_EARG;
+    }
+    for (int i = 0; i < bins; i++) out[i] = (float)nuttall(i, bins - 1);
+    return bins;
+}
+
+// e^{sign j 2 pi m / B} in fp64 with the argument reduced exactly (m mod B) and the axis points exact
+static void unit_root(long long m, int B, double sign, double* re, double* im) {
+    m %= B;
+    if (m == 0) { *re = 1.0; *im = 0.0; return; }
+    if (2 * m == B) { *re = -1.0; *im = 0.0; return; }
+    if (4 * m == B) { *re = 0.0; *im = sign; return; }
+    if (4 * m == 3 * (long long)B) { *re = 0.0; *im = -sign; return; }
+    const double th = 2.0 * DB_M_PI * (double)m / (double)B;
+    *re = std::cos(th);
+    *im = sign * std::sin(th);
+}
+
+// The FMIF kernel's matrix operand (ifnr.hip): c[n][k] = w[n] e^{-j 2 pi k n / B} as two 32 x 32
+// real tables (index n * 32 + k, zero outside n, k < B), each entry designed in fp64 from the f32
+// window value and rounded once; ph[k] = e^{+j 2 pi k floor(B/2) / B} (the back transform's
+// sample B/2, fm_if.h:67), 32 (re, im) pairs, zero for k >= B.
+int fmif_tables(int bins, float* cr, float* ci, float* ph) {
+    float w[SDRGPU_FMIF_MAX_BINS];
+    SDRGPU_CHECK(fmif_window(bins, w));
+    std::memset(cr, 0, sizeof(float) * 32 * 32);
+    std::memset(ci, 0, sizeof(float) * 32 * 32);
+    std::memset(ph, 0, sizeof(float) * 2 * 32);
+    for (int n = 0; n < bins; n++)
+        for (int k = 0; k < bins; k++) {
+            double re, im;
+            unit_root((long long)k * n, bins, -1.0, &re, &im);
+            cr[n * 32 + k] = (float)((double)w[n] * re);
+            ci[n * 32 + k] = (float)((double)w[n] * im);
+        }
+    for (int k = 0; k < bins; k++) {
+        double re, im;
+        unit_root((long long)k * (bins / 2), bins, 1.0, &re, &im);
+        ph[2 * k] = (float)re;
+        ph[2 * k + 1] = (float)im;
+    }
+    return SDRGPU_OK;
+}
+
 double hz_to_rads(double f, double fs) { return 2.0 * DB_M_PI * (f / fs); }   // math/hz_to_rads.h
 static double sinc(double x) { return (x == 0.0) ? 1.0 : (std::sin(x) / x); } // math/sinc.h
 static int estimate_tap_count(double tw, double fs) { return (int)(3.8 * fs / tw); }  // taps/estimate_tap_count.h

@@ -1,6 +1,7 @@
 // Serial (data-dependent) loops of the demodulators and the blocks composed from them:
 //   loop::AGC<T>           loop/agc.h:88-147
 //   correction::DCBlocker  correction/dc_blocker.h:54-60
+//   noise_reduction::NoiseBlanker  noise_reduction/noise_blanker.h:38-57
 //   demod::AM<T>           demod/am.h:114-142     ([carrier AGC] -> |x| -> DC block -> [audio AGC] -> LPF)
 //   demod::SSB<T>          demod/ssb.h:90-105     (xlate +-bw/2 -> Re -> AGC)
 //
@@ -178,6 +179,44 @@ __global__ __launch_bounds__(LOOP_NT) void dcb_kernel(const DT* __restrict__ in,
         __syncthreads();
     }
     if (t == 0) *st = off;
+}
+
+// noise_reduction::NoiseBlanker (noise_reduction/noise_blanker.h:38-57): the running amplitude
+// follows every non-zero sample; a sample more than `level` times above it is scaled back to it
+struct NbParams {
+    float rate, invRate, level;
+};
+__global__ __launch_bounds__(LOOP_NT) void noise_blanker_kernel(const float2* __restrict__ in, float2* __restrict__ out, int count,
+                                                               NbParams p, float* __restrict__ st) {
+    __shared__ float2 X[LOOP_CHUNK];
+    __shared__ float A[LOOP_CHUNK], G[LOOP_CHUNK];
+    const int t = threadIdx.x;
+    float amp = *st;
+    for (int i0 = 0; i0 < count; i0 += LOOP_CHUNK) {
+        const int n = min(LOOP_CHUNK, count - i0);
+        for (int i = t; i < n; i += LOOP_NT) {
+            const float2 v = in[i0 + i];
+            X[i] = v;
+            A[i] = amp_of(v);
+        }
+        __syncthreads();
+        if (t == 0) {
+            for (int i = 0; i < n; i++) {
+                const float inAmp = A[i];
+                float gain = 1.0f;
+                if (inAmp != 0.0f) {
+                    amp = (amp * p.invRate) + (inAmp * p.rate);
+                    const float excess = inAmp / amp;
+                    if (excess > p.level) gain = 1.0f / excess;
+                }
+                G[i] = gain;
+            }
+        }
+        __syncthreads();
+        for (int i = t; i < n; i += LOOP_NT) out[i0 + i] = scale_of(X[i], G[i]);
+        __syncthreads();
+    }
+    if (t == 0) *st = amp;
 }
 
 // filter::Deemphasis<T> (filter/deephasis.h:57-77): out = alpha * in + (1 - alpha) * prev,
@@ -393,6 +432,40 @@ struct DcbBlock : Block {
     }
 };
 
+struct NoiseBlankerBlock : Block {
+    NbParams p{};
+    DevBuf state;
+    void set(double rate, double level) {   // init / setRate / setLevel (noise_blanker.h:12-30): members are float
+        p.rate = (float)rate;
+        p.invRate = 1.0f - p.rate;
+        p.level = (float)level;
+    }
+    int setup(int dev, double rate, double level) {
+        device = dev;
+        in_dtype = out_dtype = SDRGPU_C64;
+        set(rate, level);
+        SDRGPU_CHECK(init_stream());
+        SDRGPU_CHECK(state.ensure(sizeof(float)));
+        return reset();
+    }
+    int out_count(int count) override { return count; }
+    int reset() override {   // noise_blanker.h:32-36
+        SDRGPU_SET_DEVICE(device);
+        const float one = 1.0f;
+        SDRGPU_HIP(hipMemcpy(state.p, &one, sizeof(one), hipMemcpyHostToDevice));
+        return SDRGPU_OK;
+    }
+    int run(const void* in, int count, void* out, hipStream_t s) override {
+        if (count < 0) { set_error("noise_blanker: negative count"); return SDRGPU_EARG; }
+        if (count == 0) return 0;
+        SDRGPU_SET_DEVICE(device);
+        hipLaunchKernelGGL(noise_blanker_kernel, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, p,
+                           state.as<float>());
+        SDRGPU_HIP(hipGetLastError());
+        return count;
+    }
+};
+
 struct DeempBlock : Block {
     float alpha = 1.0f;
     DevBuf state;
@@ -600,6 +673,8 @@ using namespace sdrgpu;
 namespace {
 int wrap_block(sdrgpu_block** h, Block* b, int rc) {
     if (rc < 0) { delete b; return rc; }
+    // creation-time state (null-stream memsets / copies) complete before the first call (blocks.hip wrap)
+    if (hipDeviceSynchronize() != hipSuccess) { delete b; set_error("hipDeviceSynchronize failed at create"); return SDRGPU_EHIP; }
     *h = new sdrgpu_block{b};
     return SDRGPU_OK;
 }
@@ -653,6 +728,19 @@ extern "C" int sdrgpu_dc_blocker_create(sdrgpu_block** h, int device, int dtype,
     if (!h || (dtype != SDRGPU_F32 && dtype != SDRGPU_C64)) { set_error("dc_blocker_create: bad argument"); return SDRGPU_EARG; }
     auto* d = new DcbBlock();
     return wrap_block(h, d, d->setup(device, dtype, rate));
+}
+
+// noise_reduction::NoiseBlanker (noise_blanker.h): the setters keep the running amplitude
+extern "C" int sdrgpu_noise_blanker_create(sdrgpu_block** h, int device, double rate, double level) {
+    if (!h) { set_error("noise_blanker_create: null handle pointer"); return SDRGPU_EARG; }
+    auto* b = new NoiseBlankerBlock();
+    return wrap_block(h, b, b->setup(device, rate, level));
+}
+extern "C" int sdrgpu_noise_blanker_set(sdrgpu_block* h, double rate, double level) {
+    auto* b = h ? dynamic_cast<NoiseBlankerBlock*>(h->impl) : nullptr;
+    if (!b) { set_error("not a noise blanker"); return SDRGPU_EARG; }
+    b->set(rate, level);
+    return SDRGPU_OK;
 }
 
 // demod::AM<T> (am.h:27-49, 114-142): agcMode 0 OFF, 1 CARRIER, 2 AUDIO; stereo -> stereo_t out

@@ -104,6 +104,8 @@ int taps_high_pass(double cutoff, double tw, double fs, int odd, float* out);
 int taps_band_pass_f(double start, double stop, double tw, double fs, int odd, float* out);
 int taps_band_pass_c(double start, double stop, double tw, double fs, int odd, float* out);
 int decim_plan(int ratio, int* decims, int* ntaps, const float** taps);
+int fmif_window(int bins, float* out);
+int fmif_tables(int bins, float* cr, float* ci, float* ph);   // 32 x 32, 32 x 32, 32 x 2 floats
 double hz_to_rads(double f, double fs);
 double xlator_effective_omega(double offsetRad);
 

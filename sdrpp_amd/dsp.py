@@ -431,6 +431,55 @@ class AGC(Block):
         return g.value
 
 
+class FMIF(Block):
+    """dsp::noise_reduction::FMIF (noise_reduction/fm_if.h): the radio module's "IF Noise
+    Reduction"; bins in [3, 32]."""
+
+    def __init__(self, bins, device=0):
+        super().__init__(_make(lib.sdrgpu_fmif_create, device, int(bins)), np.complex64, np.complex64)
+        self.bins = int(bins)
+
+    def set_bins(self, bins):
+        """setBins (fm_if.h:26-34): new window, history cleared."""
+        check(lib.sdrgpu_fmif_set_bins(self._h, int(bins)))
+        self.bins = int(bins)
+
+
+def fmif_window(bins):
+    """FMIF's window (fm_if.h:112): float32 nuttall(i, bins - 1), i < bins (host only)."""
+    w = np.empty(max(int(bins), 1), dtype=np.float32)
+    check(lib.sdrgpu_fmif_window(int(bins), _fptr(w)))
+    return w
+
+
+class NoiseBlanker(Block):
+    """dsp::noise_reduction::NoiseBlanker (noise_reduction/noise_blanker.h); bit-exact recurrence."""
+
+    def __init__(self, rate, level, device=0):
+        super().__init__(_make(lib.sdrgpu_noise_blanker_create, device, float(rate), float(level)), np.complex64, np.complex64)
+
+    def set(self, rate, level):
+        """setRate / setLevel (noise_blanker.h:19-30): the running amplitude is kept."""
+        check(lib.sdrgpu_noise_blanker_set(self._h, float(rate), float(level)))
+
+
+class Squelch(Block):
+    """dsp::noise_reduction::Squelch (noise_reduction/squelch.h); level in dB. The unmute count
+    is per handle (the reference's is one static for the whole process)."""
+
+    def __init__(self, level, device=0):
+        super().__init__(_make(lib.sdrgpu_squelch_create, device, float(level)), np.complex64, np.complex64)
+
+    def set_level(self, level):
+        check(lib.sdrgpu_squelch_set_level(self._h, float(level)))
+
+    def is_muted(self):
+        """The state after the last call (waits for the queued work)."""
+        m = ctypes.c_int()
+        check(lib.sdrgpu_squelch_get_muted(self._h, ctypes.byref(m)))
+        return bool(m.value)
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
