@@ -1,0 +1,51 @@
+// What the other translation units call in blocks.hip (host side only): chains of blocks and the
+// block constructors (loops.hip), and the hooks through which a spectrum launch carries an RxVFO's
+// stages (fft.hip, frontend.hip).
+#pragma once
+#include "sdrgpu_internal.h"
+
+namespace sdrgpu {
+
+// ---- composition: a chain of blocks run back to back on one stream ------------------------------
+int chain_new(int dev, int in_dtype, int out_dtype, Block** out);
+int chain_append(Block* chain, Block* kid);   // takes the kid (deleted on error)
+int chain_size(Block* chain);
+Block* chain_kid(Block* chain, int i);
+// Constructors: the block is returned even where *rc < 0 (the caller deletes it).
+Block* make_fir_block(int dev, int dtype, int ttype, const float* taps, int n, int decim, bool stereo, int* rc);
+Block* make_xlator_block(int dev, double offsetRad, int* rc);
+Block* make_quad_block(int dev, double deviationRad, int* rc);
+// FrequencyXlator(w) -> RationalResampler<complex_t>(inSr -> outSr) with the xlator fused into the
+// first decimation stage (BroadcastFM's RDS branch, broadcast_fm.h:164-171)
+Block* make_xlate_resample_block(int dev, double inSr, double outSr, double w, int* rc);
+
+// The taps of one of host_design.cpp's designers (taps_low_pass, taps_high_pass, taps_band_pass_f: with
+// out = nullptr they return the count) into t. A negative count is passed through; none: SDRGPU_EARG.
+template <typename Fn, typename... A>
+int design_taps(std::vector<float>& t, Fn design, A... args) {
+    const int n = design(args..., nullptr);
+    if (n < 1) return n < 0 ? n : SDRGPU_EARG;
+    t.resize(n);
+    design(args..., t.data());
+    return SDRGPU_OK;
+}
+
+// ---- an RxVFO inside the spectrum launches ------------------------------------------------------
+struct VfoStage1;   // fir_rows.h
+struct TailArgs;    // fir_tail.h
+// A VFO's first stage (row kernel) run by the spectrum launches over the same device batch
+// (fft.hip, sdrgpu_fft_execute_vfo_dev / _zoom_vfo_dev): vfo_stage1_prepare fills the launch
+// arguments for a call of `count` samples at `in` without touching the VFO's state (1: fusable,
+// 0: not -- the caller then runs the VFO on its own; < 0: error); the caller launches all M / (16 *
+// RS) segment workgroups (16 segments of 128 outputs each) and the history workgroup; then
+// vfo_stage1_finish commits the stage's state and runs the VFO's remaining stages into `out`.
+int vfo_stage1_prepare(::sdrgpu_block* vfo, const void* in, int count, VfoStage1* st);
+int vfo_stage1_finish(::sdrgpu_block* vfo, const VfoStage1& st, void* out, hipStream_t s);
+// the tail of a VFO whose first stage ran in the front end's pass-A launch, as the pass-B launch
+// carries it: 1 = t / lds filled, no state changed -- the caller launches the t.G tail
+// workgroups, then calls vfo_tail_commit (stage 1 and the tail stages move on together); 0 = not
+// applicable (nothing changed: the caller then calls vfo_stage1_finish)
+int vfo_tail_prepare(::sdrgpu_block* vfo, const VfoStage1& st, void* out, TailArgs* t, size_t* lds);
+int vfo_tail_commit(::sdrgpu_block* vfo, const VfoStage1& st, const TailArgs& t);
+
+}  // namespace sdrgpu

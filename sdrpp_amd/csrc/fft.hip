@@ -30,6 +30,7 @@
 #include "fft_passes.h"
 #include "fft_onepass.h"
 #include "fft_split.h"   // (after fft_onepass.h: see there)
+#include "blocks.h"
 
 namespace sdrgpu {
 

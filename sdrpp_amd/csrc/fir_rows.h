@@ -373,18 +373,23 @@ __device__ __forceinline__ void fir_rows_segment(const FirArgs& a, long long seg
     else body(std::false_type{});
 }
 
-// A VFO's first stage (row kernel) run by the spectrum launches over the same device batch
-// (fft.hip, sdrgpu_fft_execute_vfo_dev / _zoom_vfo_dev): vfo_stage1_prepare fills the launch
-// arguments for a call of `count` samples at `in` without touching the VFO's state (1: fusable,
-// 0: not -- the caller then runs the VFO on its own; < 0: error); the caller launches all M / (16 *
-// RS) segment workgroups (16 segments of 128 outputs each) and the history workgroup; then
-// vfo_stage1_finish commits the stage's state and runs the VFO's remaining stages into `out`.
+// The row kernel on its own (blocks.hip FirBlock): four waves per workgroup, 64 / D segments per wave,
+// and the history workgroup.
+template <int D, int QP, bool XL, bool QUAD, int RS = rows_rs<D>()>
+__global__ __launch_bounds__(256) void fir_rows_kernel(FirArgs a) {
+    if (fir_hist_block<float2, XL, false>(a)) return;
+    constexpr int NG = 64 / D;
+    const int lane = threadIdx.x & 63;
+    fir_rows_segment<D, QP, XL, QUAD, RS>(a, ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * NG + lane / D, lane);
+}
+
+// A VFO's first stage (row kernel) as the spectrum launches run it over the same device batch
+// (fft.hip, sdrgpu_fft_execute_vfo_dev / _zoom_vfo_dev): the launch arguments of one call, filled by
+// vfo_stage1_prepare (blocks.h).
 struct VfoStage1 {
     FirArgs a;
     int M = 0, count = 0;
     void* out = nullptr;
 };
-int vfo_stage1_prepare(::sdrgpu_block* vfo, const void* in, int count, VfoStage1* st);
-int vfo_stage1_finish(::sdrgpu_block* vfo, const VfoStage1& st, void* out, hipStream_t s);
 
 }  // namespace sdrgpu

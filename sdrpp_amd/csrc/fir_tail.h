@@ -26,22 +26,13 @@ constexpr int TAIL_MAXS = 4;    // stages
 // (75.2 vs 58.5 us, r5m); 512- and 128-thread workgroups slower (r5o)
 constexpr int TAIL_K = 2;
 constexpr int TAIL_NT = 256;    // threads per workgroup (short calls)
-#ifndef SDRGPU_TAIL_KBIG
-#define SDRGPU_TAIL_KBIG 4
-#endif
-#ifndef SDRGPU_TAIL_NTBIG
-#define SDRGPU_TAIL_NTBIG 256
-#endif
-constexpr int TAIL_K_BIG = SDRGPU_TAIL_KBIG;     // big calls (A/B builds)
-constexpr int TAIL_NT_BIG = SDRGPU_TAIL_NTBIG;
-#ifndef SDRGPU_TAIL_PF
-#define SDRGPU_TAIL_PF 16
-#endif
-#ifndef SDRGPU_TAIL_LDSMAX
-#define SDRGPU_TAIL_LDSMAX 65536
-#endif
-constexpr int TAIL_PF = SDRGPU_TAIL_PF;     // image loads per thread issued together (A/B builds)
-constexpr int TAIL_LDSMAX = SDRGPU_TAIL_LDSMAX;   // bytes of LDS a tail workgroup may take
+constexpr int TAIL_K_BIG = 4;       // big calls (the measurements above)
+constexpr int TAIL_NT_BIG = 256;
+// image loads per thread issued together, and the LDS a tail workgroup may take: fewer, larger workgroups
+// measured slower (tail + zoom-fold launch 72.9 / 85.7 / 122.4 us at 16 / 32 / 64 loads, the last with
+// ~101 KB of LDS: profiles/r6/README.md)
+constexpr int TAIL_PF = 16;
+constexpr int TAIL_LDSMAX = 65536;
 struct TailStage {
     const float2* hist;   // H samples (newest last)
     float2* histNext;     // next call's history: [hist || in][n + k], k < H
@@ -235,11 +226,12 @@ __device__ __forceinline__ void fir_tail_block(const TailArgs& t, int w, bool la
     }
 }
 
-// the tail of a VFO whose first stage ran in the front end's pass-A launch, as the pass-B launch
-// carries it (blocks.hip): 1 = t / lds filled, no state changed -- the caller launches the t.G tail
-// workgroups, then calls vfo_tail_commit (stage 1 and the tail stages move on together); 0 = not
-// applicable (nothing changed: the caller then calls vfo_stage1_finish)
-int vfo_tail_prepare(::sdrgpu_block* vfo, const VfoStage1& st, void* out, TailArgs* t, size_t* lds);
-int vfo_tail_commit(::sdrgpu_block* vfo, const VfoStage1& st, const TailArgs& t);
+// The tail on its own (blocks.hip ChainBlock): one workgroup per tail workgroup.
+template <int K, int NT>
+__global__ __launch_bounds__(NT) void fir_tail_kernel(TailArgs t) {
+    extern __shared__ __attribute__((aligned(16))) float2 XS[];
+    __shared__ TailGeom gs[TAIL_MAXS];
+    fir_tail_block<K, NT>(t, blockIdx.x, blockIdx.x == gridDim.x - 1, XS, gs);
+}
 
 }  // namespace sdrgpu

@@ -22,6 +22,7 @@
 #include <vector>
 #include "sdrgpu_internal.h"
 #include "fir_rows.h"
+#include "blocks.h"
 
 namespace sdrgpu {
 __global__ void conjugate_kernel(float2* __restrict__ x, int n) {   // math/conjugate.h

@@ -9,7 +9,7 @@
 // (the reference runs a forward FFTW plan, keeps the peak bin and reads sample B/2 of an
 // unnormalised backward plan, per sample). Every output is independent: count x B x B complex
 // MACs = a GEMM with the samples as rows and the bins as columns, on the f32 matrix cores
-// (v_mfma_f32_16x16x4_f32, layout as fir_mfma_kernel in blocks.hip):
+// (v_mfma_f32_16x16x4_f32, layout as fir_mfma_kernel in fir_mfma.h):
 //   A[i][n] = buf[o + i + n]   Toeplitz rows of the span staged in LDS: lane (i = lane & 15,
 //                              kk = lane >> 4) reads X[o + i + 4 s + kk] at k step s, consecutive
 //                              addresses across lanes (conflict-free);

@@ -24,6 +24,7 @@
 #include <memory>
 #include <vector>
 #include "sdrgpu_internal.h"
+#include "blocks.h"
 
 namespace sdrgpu {
 
@@ -526,19 +527,8 @@ static std::unique_ptr<MapBlock> make_map(int dev, int kind) {
     return m;
 }
 
-// A chain of blocks run back to back on one stream (defined in blocks.hip)
-int chain_new(int dev, int in_dtype, int out_dtype, Block** out);
-int chain_append(Block* chain, Block* kid);
-int chain_size(Block* chain);
-Block* chain_kid(Block* chain, int i);
-Block* make_fir_block(int dev, int dtype, int ttype, const float* taps, int n, int decim, bool stereo, int* rc);
-Block* make_xlator_block(int dev, double offsetRad, int* rc);
-
-
 // BroadcastFM (demod/broadcast_fm.h:34-60, 144-215): quadrature -> [stereo: pilot band-pass
 // (complex, 305 taps at 240 kS/s) -> PLL -> matrix] -> audio low-pass -> stereo_t
-Block* make_quad_block(int dev, double deviationRad, int* rc);
-Block* make_xlate_resample_block(int dev, double inSr, double outSr, double w, int* rc);
 struct BroadcastFmBlock : Block {
     bool stereo = true, lowPass = true;
     std::unique_ptr<Block> quad, pilot, audio;
@@ -596,10 +586,8 @@ struct BroadcastFmBlock : Block {
         pp.maxFreq = (float)hz_to_rads(19250.0, samplerate);
         initPhase = 0.0f;
         initFreq = (float)hz_to_rads(19000.0, samplerate);
-        const int na = taps_low_pass(15000.0, 4000.0, samplerate, 0, nullptr);
-        if (na < 1) return na < 0 ? na : SDRGPU_EARG;
-        std::vector<float> at(na);
-        taps_low_pass(15000.0, 4000.0, samplerate, 0, at.data());
+        std::vector<float> at;
+        SDRGPU_CHECK(design_taps(at, taps_low_pass, 15000.0, 4000.0, samplerate, 0));
         if (!lowPass) { at.assign(1, 1.0f); }                          // identity: raw L/R (or MPX) pairs
         // (l, r) pairs filtered as one complex stream with real taps = alFir / arFir
         audio.reset(make_fir_block(dev, SDRGPU_C64, SDRGPU_F32, at.data(), (int)at.size(), 1, false, &rc));
@@ -768,12 +756,10 @@ extern "C" int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, doubl
     }
     if (rc >= 0) {
         const double fc = bandwidth / 2.0;
-        const int n = taps_low_pass(fc, fc * 0.1, samplerate, 0, nullptr);
-        rc = n < 1 ? (n < 0 ? n : SDRGPU_EARG) : SDRGPU_OK;
+        std::vector<float> t;
+        rc = design_taps(t, taps_low_pass, fc, fc * 0.1, samplerate, 0);
         if (rc >= 0) {
-            std::vector<float> t(n);
-            taps_low_pass(fc, fc * 0.1, samplerate, 0, t.data());
-            Block* f = make_fir_block(device, SDRGPU_F32, SDRGPU_F32, t.data(), n, 1, stereo != 0, &rc);
+            Block* f = make_fir_block(device, SDRGPU_F32, SDRGPU_F32, t.data(), (int)t.size(), 1, stereo != 0, &rc);
             if (rc >= 0) rc = chain_append(c, f); else delete f;
         }
     }

@@ -135,9 +135,6 @@ struct Block {
     virtual int reset() = 0;
 };
 
-// kernels (fir.hip / fft.hip)
-struct FirState;   // defined in fir.hip
-
 }  // namespace sdrgpu
 
 struct sdrgpu_block {

@@ -360,6 +360,31 @@ def test_ddc_c3_fir_stage(rng):
         assert_close_c(yg, yo, fir_atol(taps, x) if n else 0, "C3 FIR stage")
 
 
+def test_ddc_rows_zero_output_calls():
+    """The row kernel with the fused xlator (D = 32, 143 taps: the RxVFO stage-1 shape) across calls
+    that yield no output: calls two to four (7, 0 and 5 samples) fall inside the decimation phase
+    left by the first, so their history is carried by fir_hist_kernel<float2, true> from the
+    per-call NCO table while the row kernel (which forms its phasors itself) is the one selected.
+    Output counts equal the oracle's on every call; every output within fir_atol of the oracle's
+    xlator -> fp64-accumulated FIR. (A generator of its own: the session's one hands every later
+    test the inputs it had before this test existed.)"""
+    rng = np.random.default_rng(0x9D0C)
+    taps = (rng.standard_normal(143) / 143).astype(np.float32)
+    w = 2 * np.pi * (-2.5e6 / 61.44e6)
+    g = dsp.DDC(w, taps, 32)
+    ox, of = oracle.Xlator(w), oracle.FIR(taps, 32)
+    counts = []
+    for n in [1000, 7, 0, 5, 40000]:
+        x = iq(rng, n)
+        yo = of.process(ox.process(x))
+        yg = g.process(x)
+        assert len(yg) == len(yo), (n, len(yg), len(yo))
+        counts.append(len(yg))
+        if len(yo):
+            assert_close_c(yg, yo, fir_atol(taps, x), f"rows DDC, call of {n}")
+    assert counts[1:4] == [0, 0, 0] and counts[0] > 0 and counts[4] > 0, counts
+
+
 def _quad64(y, yprev0, inv_dev):
     """fp64 quadrature (quadrature.h:41-56) of an FIR output stream."""
     y = np.asarray(y, np.complex128)

@@ -5,7 +5,7 @@
 
 Cases: RxVFO (C5: 61.44 MHz -> 240 kHz) over ragged host calls; BroadcastFM mono on one big call; the C5 launch group (spectrum rows,
 zoom rows, VFO stage-1 + later stages) over 24 frames; the standalone spectrum over 24 frames; the fp64-interior
-spectrum (64k over 300 frames, 1M over 3)."""
+spectrum (64k over 300 frames, 1M over 3); the channel-chain kernels none of these reach (chain_cases)."""
 import hashlib
 import json
 import os
@@ -57,7 +57,41 @@ def main():
         dsp.FFTSpectrum(n, nz, 6, precision="f64").execute_dev(xs.data_ptr(), nz, f, r.data_ptr())
         torch.cuda.synchronize()
         out[f"spectrum_f64_{n}"] = h(r.cpu().numpy())
+    chain_cases(out, h)
     print(json.dumps(out))
+
+
+def chain_cases(out, h):
+    """The channel-chain kernels the cases above do not reach, each over 400,000 samples in ragged host
+    calls of 100,001 / 0 (empty) / 1 (no output at any decimation >= 2: the history kernel) / 150,005 /
+    149,993 samples."""
+    from sdrpp_amd import dsp
+    rng = np.random.default_rng(4321)
+    x = (rng.uniform(-1, 1, 400000) + 1j * rng.uniform(-1, 1, 400000)).astype(np.complex64)
+    cuts = [100001, 100001, 100002, 250007]
+
+    def run(block, data):
+        return h(np.concatenate([block.process(p) for p in np.split(data, cuts)]).view(np.uint32))
+
+    fs = 61.44e6
+    w = 2 * np.pi * (-1.5e6 / fs)
+    c3 = dsp.low_pass(3.0e6, 912000.0, fs)   # the 256-tap C3 low-pass
+
+    def rt(n):
+        return (rng.standard_normal(n) / n).astype(np.float32)
+
+    out["ddcfm_d8_256"] = run(dsp.DDCFM(w, c3, 8, 2 * np.pi * 100e3 / (fs / 8)), x)   # fir_mfma_kernel + quadrature
+    out["ddc_d8_256"] = run(dsp.DDC(w, c3, 8), x)                                     # fir_mfma_kernel
+    out["ddc_d4_27"] = run(dsp.DDC(w, rt(27), 4), x)                                  # fir_mfma_ps_kernel
+    out["fir_real_d2_69"] = run(dsp.FIR(rt(69), 2, complex_data=False), x.real.copy())   # fir_kernel<float, float>
+    out["fir_ctaps_d3_305"] = run(dsp.FIR(rt(305) + 1j * rt(305), 3), x)              # fir_kernel<float2, float2>
+    out["fir_d128_726"] = run(dsp.FIR(rt(726), 128), x)                               # tile search: shrinking branch
+    out["poly_3_2"] = run(dsp.PolyphaseResampler(3, 2, rt(96)), x)
+    wfm = dsp.BroadcastFM(100000, 240000, True)   # 1,200-sample calls: wfm_short_kernel
+    out["wfm_short"] = h(np.concatenate([wfm.process(p) for p in np.split(x[:3177], [1200, 2400, 2400])]).view(np.uint32))
+    codes = rng.integers(-32768, 32768, 4096).astype(np.int16)
+    out["convert_i16"] = h(dsp.convert(1, codes))
+    out["convert_mono_i16"] = h(dsp.convert_mono(1, codes))
 
 
 if __name__ == "__main__":
