@@ -1,6 +1,7 @@
 // What the other translation units call in blocks.hip (host side only): chains of blocks and the
-// block constructors (loops.hip), and the hooks through which a spectrum launch carries an RxVFO's
-// stages (fft.hip, frontend.hip).
+// block constructors (loops.hip), the publication of a new handle and the history carry (loops.hip,
+// channelizer.hip, ifnr.hip), and the hooks through which a spectrum launch carries an RxVFO's stages
+// (fft.hip, frontend.hip).
 #pragma once
 #include "sdrgpu_internal.h"
 
@@ -29,6 +30,25 @@ int design_taps(std::vector<float>& t, Fn design, A... args) {
     design(args..., t.data());
     return SDRGPU_OK;
 }
+
+// ---- publication and ordering --------------------------------------------------------------------
+// Every create function ends in publish_block: rc < 0 deletes b and passes rc on; else the device is
+// synchronised and *h becomes the new handle.
+// The ordering rule, stated once: a block's calls run on non-blocking streams, which the null stream
+// does not order, so a C entry point that wrote device state on the null stream (a memset or a copy
+// in setup(), reset() or a setter) ends with hipDeviceSynchronize(). That is publish_block for a
+// create, sdrgpu_block_reset for a reset, and the setter itself otherwise (sdrgpu_fmif_set_bins;
+// sdrgpu_broadcast_fm_set_rds when it builds the RDS chain). Block::reset() implementations do not
+// synchronise: a chain's reset pays for one, not one per kid. (A setter whose only device write is a
+// blocking hipMemcpy from host memory, AgcBlock::set_gain, has nothing pending when it returns.)
+int publish_block(::sdrgpu_block** h, Block* b, int rc);
+
+// The history carry on its own launch (fir_hist_kernel): next = the last H elements (of dtype) of
+// [hist || in] after `count` inputs. nco (non-null, C64): the fused xlator applied to the `in` samples,
+// from its per-call table.
+struct Nco;
+int carry_history(int dtype, const Nco* nco, const DevBuf& hist, const void* in, DevBuf& next, int H, int count,
+                  hipStream_t s);
 
 // ---- an RxVFO inside the spectrum launches ------------------------------------------------------
 struct VfoStage1;   // fir_rows.h

@@ -13,7 +13,7 @@
 //      (make_fir, make_xlator, make_quad_block, new_chain), PowerDecimator / RationalResampler
 //      composition, VfoBlock, WfmBlock;
 //   6. the hooks of a VFO carried by the spectrum launches (vfo_stage1_* / vfo_tail_*);
-//   7. the C ABI: create functions (one wrap() each), process / reset / destroy, converters.
+//   7. the C ABI: create functions (one publish_block() each), process / reset / destroy, converters.
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -139,9 +139,9 @@ struct Nco {
     }
 };
 
-// The history carry on its own launch (fir_hist_kernel): next = the last H samples of [hist | in] after
-// `count` inputs; nco (non-null): the fused xlator applied to the `in` samples, from its per-call table.
-static int carry_history(int dtype, const Nco* nco, const DevBuf& hist, const void* in, DevBuf& next, int H, int count,
+// The history carry on its own launch (blocks.h): FirBlock's zero-output call, PolyBlock, BroadcastFM's
+// delay line (loops.hip) and the channelizer (channelizer.hip).
+int carry_history(int dtype, const Nco* nco, const DevBuf& hist, const void* in, DevBuf& next, int H, int count,
                          hipStream_t s) {
     const dim3 g((H + 255) / 256), b(256);
     if (dtype == SDRGPU_F32) {
@@ -821,7 +821,7 @@ struct ChainBlock : Block {
 };
 
 // ------------------------------------------------------- block constructors
-// (each returns its block even where *rc < 0: the caller deletes it, or wrap() does)
+// (each returns its block even where *rc < 0: the caller deletes it, or publish_block() does)
 static std::unique_ptr<FirBlock> make_fir(int dev, int dtype, int ttype, const float* taps, int n, int decim, int* rc,
                                           bool xl = false, double w = 0.0, bool quad = false, float invDev = 1.0f,
                                           bool stereo = false) {
@@ -1052,21 +1052,23 @@ int vfo_stage1_finish(sdrgpu_block* vfo, const VfoStage1& st, void* out, hipStre
     return c->run_rest(st.out, st.M, out, s);
 }
 
-}  // namespace sdrgpu
-
-using namespace sdrgpu;
-
-// ================================================================== C ABI
-static int wrap(sdrgpu_block** h, Block* b, int rc) {
+// The one way a create function hands a new block to its caller (blocks.h states the ordering rule).
+int publish_block(::sdrgpu_block** h, Block* b, int rc) {
     if (rc < 0) { delete b; return rc; }
     // The state written at creation (reset(): memsets / copies on the null stream) must be complete
     // before the first call, which runs on a non-blocking stream the null stream does not order:
     // a handle whose buffer recycled non-zero memory otherwise may start from it (seen once per
     // process on a fresh Quadrature: y[-1] != 0).
     if (hipDeviceSynchronize() != hipSuccess) { delete b; set_error("hipDeviceSynchronize failed at create"); return SDRGPU_EHIP; }
-    *h = new sdrgpu_block{b};
+    *h = new ::sdrgpu_block{b};
     return SDRGPU_OK;
 }
+
+}  // namespace sdrgpu
+
+using namespace sdrgpu;
+
+// ================================================================== C ABI
 #define NEED_HANDLE(h) do { if (!(h) || !(h)->impl) { set_error("null block handle"); return SDRGPU_EARG; } } while (0)
 #define NEED_OUT(h) do { if (!(h)) { set_error("null out-handle"); return SDRGPU_EARG; } } while (0)
 
@@ -1074,7 +1076,7 @@ extern "C" int sdrgpu_xlator_create(sdrgpu_block** h, int device, double offsetR
     NEED_OUT(h);
     int rc;
     Block* x = make_xlator_block(device, offsetRad, &rc);
-    return wrap(h, x, rc);
+    return publish_block(h, x, rc);
 }
 extern "C" int sdrgpu_xlator_set_offset(sdrgpu_block* h, double offsetRad) {
     NEED_HANDLE(h);
@@ -1092,7 +1094,7 @@ extern "C" int sdrgpu_fir_create(sdrgpu_block** h, int device, int dtype, int tt
     }
     int rc;
     auto f = make_fir(device, dtype, ttype, taps, ntaps, decim, &rc);
-    return wrap(h, f.release(), rc);
+    return publish_block(h, f.release(), rc);
 }
 extern "C" int sdrgpu_fir_set_taps(sdrgpu_block* h, const float* taps, int ntaps) {
     NEED_HANDLE(h);
@@ -1111,7 +1113,7 @@ extern "C" int sdrgpu_quadrature_create(sdrgpu_block** h, int device, double dev
     NEED_OUT(h);
     int rc;
     Block* q = make_quad_block(device, deviationRad, &rc);
-    return wrap(h, q, rc);
+    return publish_block(h, q, rc);
 }
 extern "C" int sdrgpu_quadrature_set_deviation(sdrgpu_block* h, double deviationRad) {
     NEED_HANDLE(h);
@@ -1130,14 +1132,14 @@ extern "C" int sdrgpu_power_decimator_create(sdrgpu_block** h, int device, int d
     int rc;
     auto* c = new_chain(device, dtype, dtype, &rc);
     if (rc >= 0) rc = build_power_decim(c, device, dtype, ratio, false, 0.0);
-    return wrap(h, c, rc);
+    return publish_block(h, c, rc);
 }
 
 extern "C" int sdrgpu_polyphase_resampler_create(sdrgpu_block** h, int device, int dtype, int interp, int decim,
                                                  const float* taps, int ntaps) {
     NEED_OUT(h);
     auto* p = new PolyBlock();
-    return wrap(h, p, p->setup(device, dtype, interp, decim, taps, ntaps));
+    return publish_block(h, p, p->setup(device, dtype, interp, decim, taps, ntaps));
 }
 
 extern "C" int sdrgpu_rational_resampler_create(sdrgpu_block** h, int device, int dtype, double inSr, double outSr) {
@@ -1145,7 +1147,7 @@ extern "C" int sdrgpu_rational_resampler_create(sdrgpu_block** h, int device, in
     int rc;
     auto* c = new_chain(device, dtype, dtype, &rc);
     if (rc >= 0) rc = build_rational(c, device, dtype, inSr, outSr, false, 0.0);
-    return wrap(h, c, rc);
+    return publish_block(h, c, rc);
 }
 
 extern "C" int sdrgpu_rxvfo_create(sdrgpu_block** h, int device, double inSr, double outSr, double bw, double offset) {
@@ -1154,7 +1156,7 @@ extern "C" int sdrgpu_rxvfo_create(sdrgpu_block** h, int device, double inSr, do
     auto* v = new_chain<VfoBlock>(device, SDRGPU_C64, SDRGPU_C64, &rc);
     v->inSr = inSr; v->outSr = outSr; v->bw = bw; v->offset = offset;
     if (rc >= 0) rc = v->build();
-    return wrap(h, v, rc);
+    return publish_block(h, v, rc);
 }
 extern "C" int sdrgpu_rxvfo_set_offset(sdrgpu_block* h, double offset) {
     NEED_HANDLE(h);
@@ -1169,7 +1171,7 @@ extern "C" int sdrgpu_ddc_fm_create(sdrgpu_block** h, int device, double offsetR
     int rc;
     auto f = make_fir(device, SDRGPU_C64, SDRGPU_F32, taps, ntaps, decim, &rc, true, xlator_effective_omega(offsetRad),
                       true, (float)(1.0 / deviationRad));
-    return wrap(h, f.release(), rc);
+    return publish_block(h, f.release(), rc);
 }
 
 // Fused DDC without the demodulator: FrequencyXlator(offsetRad) -> DecimatingFIR<complex_t,float>
@@ -1179,7 +1181,7 @@ extern "C" int sdrgpu_ddc_create(sdrgpu_block** h, int device, double offsetRad,
     NEED_OUT(h);
     int rc;
     auto f = make_fir(device, SDRGPU_C64, SDRGPU_F32, taps, ntaps, decim, &rc, true, xlator_effective_omega(offsetRad));
-    return wrap(h, f.release(), rc);
+    return publish_block(h, f.release(), rc);
 }
 
 // FM<float> (demod/fm.h:25-133): quadrature(bw/2) -> optional LPF/HPF/BPF
@@ -1198,7 +1200,7 @@ extern "C" int sdrgpu_fm_create(sdrgpu_block** h, int device, double samplerate,
             if (rc >= 0) c->kids.push_back(std::move(f));
         }
     }
-    return wrap(h, c, rc);
+    return publish_block(h, c, rc);
 }
 
 // BroadcastFM, stereo == false (demod/broadcast_fm.h:144-215): quadrature(dev) ->
@@ -1215,7 +1217,7 @@ extern "C" int sdrgpu_wfm_create(sdrgpu_block** h, int device, double deviation,
         auto f = make_fir(device, SDRGPU_F32, SDRGPU_F32, t.data(), (int)t.size(), 1, &rc, false, 0.0, false, 1.0f, true);
         if (rc >= 0) c->kids.push_back(std::move(f));
     }
-    return wrap(h, c, rc);
+    return publish_block(h, c, rc);
 }
 
 extern "C" int sdrgpu_block_out_count(sdrgpu_block* h, int count) {

@@ -177,3 +177,79 @@ def test_broadcast_fm_stereo_mono_path_equals_wfm(rng):
     a = dsp.BroadcastFM(100000, fs, True, stereo=False).process(x)
     o = oracle.BroadcastFMStereo(100000, fs, False, True).process(x)
     assert np.abs(a["l"] - o["l"]).max() <= 2e-5 and np.array_equal(a["l"], a["r"])
+
+
+CHUNK_CUTS = [1, 1023, 1024, 1025, 0, 2049, 37]
+
+
+def _chunk_edge_cases():
+    """(name, block, oracle, stream): each serial block with the oracle its own bit-exact test uses, on
+    sum(CHUNK_CUTS) samples from a generator of this test's own (the session `rng` is not advanced)."""
+    from test_ifnr import NoiseBlankerRef, bursty as if_bursty
+    rng = np.random.default_rng(0x10C5)
+    n = sum(CHUNK_CUTS)
+    rate = 10.0 / 48000
+    yield ("dcb_f32", dsp.DCBlocker(rate, False), oracle.DCBlocker(rate, False),
+           (rng.uniform(-1, 1, n) + 0.25).astype(np.float32))
+    yield ("dcb_c64", dsp.DCBlocker(rate, True), oracle.DCBlocker(rate, True),
+           (iq(rng, n) + (0.3 + 0.2j)).astype(np.complex64))
+    yield ("deemp_mono", dsp.Deemphasis(50e-6, 48000, False), oracle.Deemphasis(50e-6, 48000, False),
+           rng.uniform(-1, 1, n).astype(np.float32))
+    st = np.zeros(n, dsp.STEREO)
+    st["l"], st["r"] = rng.uniform(-1, 1, n), rng.uniform(-1, 1, n)
+    yield ("deemp_stereo", dsp.Deemphasis(50e-6, 48000, True), oracle.Deemphasis(50e-6, 48000, True), st)
+    for rate, level in [(500.0 / 24000.0, 10.0), (500.0 / 250000.0, 2.0)]:   # test_noise_blanker_bit_exact's
+        yield (f"nb_{level:g}", dsp.NoiseBlanker(rate, level), NoiseBlankerRef(rate, level), if_bursty(rng, n))
+
+
+def test_serial_blocks_chunk_edges():
+    """The serial blocks' walk stages 1024 samples at a time: calls of 1 / 1023 / 1024 / 1025 / 0 / 2049 /
+    37 samples put a call's end before, on and after a chunk edge and run two full chunks plus one sample
+    in one call. Every call's output is bit-identical to the block's oracle."""
+    def bits(a):
+        return np.ascontiguousarray(a).view(np.uint32)
+
+    for name, g, o, x in _chunk_edge_cases():
+        i = 0
+        for c in CHUNK_CUTS:
+            a, b = g.process(x[i:i + c]), o.process(x[i:i + c])
+            assert a.shape == b.shape and np.array_equal(bits(a), bits(b)), f"{name}: call of {c} at {i}"
+            i += c
+        assert i == len(x)
+
+
+def test_broadcast_fm_stereo_split_invariant():
+    """BroadcastFM stereo with RDS, one call against the same stream in seven: l and r are bit-identical.
+    The state (PLL phase / frequency, the delay line, every FIR history) is on the device, the FIR streams
+    are split-invariant and the libm calls deterministic. Calls shorter than, equal to and longer than the
+    delay line exercise the hist / in split of its carry; 1024 and 1025 cross a chunk edge of the PLL walk.
+
+    The RDS samples are not bit-identical between the two cuttings (seen before this test's code was
+    touched: the last bits differ, 1e-9 at a 1e-3 sample): the branch's xlator reads a per-call NCO table
+    built from the call's start phase, so where a call starts moves the table's rounding. They are held to
+    equal counts per stream and to the cascade bar of test_broadcast_fm_rds_branch, 5e-5 of the MPX peak."""
+    fs = 240000.0
+    ntaps = len(oracle.band_pass(18750.0, 19250.0, 3000.0, fs, True, complex_taps=True))   # the pilot filter
+    delay = (ntaps - 1) // 2 + 1
+    assert (ntaps, delay) == (305, 153)
+    cuts = [1, delay - 1, delay, delay + 1, 1024, 1025, 700]
+    n = sum(cuts)
+    x = fm_stereo_iq(n, fs)
+    one = dsp.BroadcastFM(100000, fs, True, stereo=True, rds=True)
+    whole = one.process(x)
+    whole_rds = one.rds_output()
+    many = dsp.BroadcastFM(100000, fs, True, stereo=True, rds=True)
+    audio, rds = [], []
+    i = 0
+    for c in cuts:
+        audio.append(many.process(x[i:i + c]))
+        rds.append(many.rds_output())
+        i += c
+    audio, rds = np.concatenate(audio), np.concatenate(rds)
+    assert audio.shape == whole.shape == (n,) and rds.shape == whole_rds.shape and len(rds) > 50
+    for ch in ("l", "r"):
+        assert np.array_equal(audio[ch].view(np.uint32), whole[ch].view(np.uint32)), ch
+    mpx_peak = np.abs(oracle.Quadrature(2 * np.pi * 100000 / fs).process(x)).max()
+    err = np.abs(rds - whole_rds).max()
+    print(f"rds split vs whole: max diff {err:.3e}, bar {5e-5 * mpx_peak:.3e}")
+    assert err <= 5e-5 * mpx_peak

@@ -5,7 +5,8 @@
 
 Cases: RxVFO (C5: 61.44 MHz -> 240 kHz) over ragged host calls; BroadcastFM mono on one big call; the C5 launch group (spectrum rows,
 zoom rows, VFO stage-1 + later stages) over 24 frames; the standalone spectrum over 24 frames; the fp64-interior
-spectrum (64k over 300 frames, 1M over 3); the channel-chain kernels none of these reach (chain_cases)."""
+spectrum (64k over 300 frames, 1M over 3); the channel-chain kernels none of these reach (chain_cases); the serial
+loops, the demodulators built on them, the IF noise reduction blocks and the channelizer (loop_cases)."""
 import hashlib
 import json
 import os
@@ -58,6 +59,7 @@ def main():
         torch.cuda.synchronize()
         out[f"spectrum_f64_{n}"] = h(r.cpu().numpy())
     chain_cases(out, h)
+    loop_cases(out, h)
     print(json.dumps(out))
 
 
@@ -92,6 +94,62 @@ def chain_cases(out, h):
     codes = rng.integers(-32768, 32768, 4096).astype(np.int16)
     out["convert_i16"] = h(dsp.convert(1, codes))
     out["convert_mono_i16"] = h(dsp.convert_mono(1, codes))
+
+
+def loop_cases(out, h):
+    """loops.hip, ifnr.hip and channelizer.hip: each block over 300,000 samples in ragged host calls of
+    70,001 / 0 (empty) / 1 / 1,024 / 120,003 / 108,971 samples (the serial blocks walk 1024-sample chunks);
+    the channelizers over 48 M + 333 / 0 / 1 / 17 M - 5 samples."""
+    from sdrpp_amd import dsp
+    rng = np.random.default_rng(8765)
+    n = 300000
+    x = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex64)
+    env = np.repeat(10.0 ** rng.uniform(-3, 0, n // 500 + 1), 500)[:n].astype(np.float32)
+    xb = (x * env).astype(np.complex64)          # level steps over 60 dB, a silent gap, spikes: every AGC /
+    xb[n // 3:n // 3 + 700] = 0                  # blanker branch runs
+    xb[rng.integers(0, n, 40)] *= 50
+    cuts = np.cumsum([70001, 0, 1, 1024, 120003])
+
+    def run(block, data, view=np.uint32):
+        return h(np.concatenate([np.ascontiguousarray(block.process(p)) for p in np.split(data, cuts)]).view(view))
+
+    agc = (1.0, 50.0 / 48000, 5.0 / 48000, 10e6, 10.0, float("inf"))
+    out["agc_f32"] = run(dsp.AGC(*agc, complex_data=False), xb.real.copy())
+    out["agc_c64"] = run(dsp.AGC(*agc, complex_data=True), xb)
+    out["dcb_c64"] = run(dsp.DCBlocker(10.0 / 48000, True), (x + np.complex64(0.3 + 0.2j)).astype(np.complex64))
+    st = np.zeros(n, dsp.STEREO)
+    st["l"], st["r"] = x.real, x.imag
+    out["deemp_stereo"] = run(dsp.Deemphasis(50e-6, 48000, True), st)
+    out["noise_blanker"] = run(dsp.NoiseBlanker(500.0 / 24000.0, 10.0), xb)
+    fs = 48000.0
+    out["am_mode1"] = run(dsp.AM(1, 10000.0, 50.0 / fs, 5.0 / fs, 10.0 / fs, fs), (0.05 * xb).astype(np.complex64))
+    out["ssb_mode0_agc"] = run(dsp.SSB(0, 2800.0, 24000.0, True, 50.0 / 24000, 5.0 / 24000), (0.2 * xb).astype(np.complex64))
+    # BroadcastFM stereo with RDS at 240 kS/s: a pilot, L - R on the 38 kHz subcarrier, a 57 kHz RDS-like carrier
+    fm_fs = 240000.0
+    t = np.arange(n) / fm_fs
+    mpx = (0.45 * np.sin(2 * np.pi * 1000 * t) * (1 + np.cos(2 * np.pi * 38000 * t)) + 0.1 * np.cos(2 * np.pi * 19000 * t)
+           + 0.05 * np.sign(np.sin(2 * np.pi * 1187.5 * t)) * np.cos(2 * np.pi * 57000 * t))
+    iqfm = (0.5 * np.exp(2j * np.pi * 75000 * np.cumsum(mpx) / fm_fs) + 1e-3 * x).astype(np.complex64)
+    bfm = dsp.BroadcastFM(100000, fm_fs, True, stereo=True, rds=True)
+    audio, rds = [], []
+    for p in np.split(iqfm, cuts):
+        audio.append(np.ascontiguousarray(bfm.process(p)))
+        rds.append(bfm.rds_output())
+    out["bfm_stereo_audio"] = h(np.concatenate(audio).view(np.uint32))
+    out["bfm_stereo_rds"] = h(np.concatenate(rds).view(np.uint32))
+    for bins in (15, 32):
+        out[f"fmif_b{bins}"] = run(dsp.FMIF(bins), x)
+    # Squelch at -30 dB over calls at -6 / -60 / -6 dB: mutes on the first quiet call, unmutes after ten loud ones
+    sq = dsp.Squelch(-30.0)
+    lv = [0.5] * 2 + [1e-3] * 3 + [0.5] * 13
+    out["squelch_step"] = h(np.concatenate([sq.process((g * x[k * 4099:(k + 1) * 4099]).astype(np.complex64))
+                                            for k, g in enumerate(lv)]).view(np.uint32))
+    for M, dft in ((256, "fft"), (1024, "fft"), (1024, "gemm")):
+        taps = (rng.standard_normal(16 * M - 7) / (16 * M)).astype(np.float32)
+        ch = dsp.PolyphaseChannelizer(M, taps, dft=dft)
+        ccuts = np.cumsum([48 * M + 333, 0, 1])
+        ys = [ch.process(p) for p in np.split(x[:48 * M + 333 + 1 + 17 * M - 5], ccuts)]
+        out[f"chan_{M}_{dft}"] = h(np.concatenate(ys).view(np.uint32))
 
 
 if __name__ == "__main__":
