@@ -27,6 +27,9 @@
  *   FM        : dsp::demod::FM<float>::process, dsp/demod/fm.h:86-103
  *   WFM       : dsp::demod::BroadcastFM::process (mono), dsp/demod/broadcast_fm.h:144-215
  *   ingest    : file_source converters, source_modules/file_source/src/main.cpp:361-542
+ *   symbols   : loop::FastAGC, loop::Costas, clock_recovery::MM, digital::BinarySlicer,
+ *               digital::DifferentialDecoder, demod::PSK, demod::GFSK (dsp/loop/fast_agc.h, dsp/loop/costas.h,
+ *               dsp/clock_recovery/mm.h, dsp/digital/, dsp/demod/psk.h, dsp/demod/gfsk.h)
  */
 #ifndef SDRGPU_H
 #define SDRGPU_H
@@ -50,7 +53,8 @@ enum {
 };
 
 /* element types (dsp::complex_t is {float re, im}, dsp/types.h:6; stereo_t {float l, r}) */
-enum { SDRGPU_F32 = 0, SDRGPU_C64 = 1 };
+/* SDRGPU_U8: uint8_t symbols / bits (digital/binary_slicer.h, digital/differential_decoder.h) */
+enum { SDRGPU_F32 = 0, SDRGPU_C64 = 1, SDRGPU_U8 = 2 };
 
 /* window ids = dsp::window::windowType (dsp/window/window.h:27-35) */
 enum { SDRGPU_WIN_RECTANGULAR = 0, SDRGPU_WIN_HAMMING, SDRGPU_WIN_HANN, SDRGPU_WIN_BLACKMAN,
@@ -83,6 +87,15 @@ int  sdrgpu_taps_high_pass(double cutoff, double transWidth, double sampleRate, 
 int  sdrgpu_taps_band_pass_f(double start, double stop, double transWidth, double sampleRate, int odd, float* out); /* band_pass.h:11 */
 int  sdrgpu_taps_band_pass_c(double start, double stop, double transWidth, double sampleRate, int odd, float* out);
 int  sdrgpu_decim_plan(int ratio, int* decims, int* ntaps, const float** taps);      /* decim/plans.h */
+/* taps::rootRaisedCosine<float>(count, beta, Ts) (taps/root_raised_cosine.h:8-29), Ts = samplerate /
+ * symbolrate; fp64, rounded once; out NULL -> count */
+int  sdrgpu_taps_root_raised_cosine(int count, double beta, double Ts, float* out);
+/* host only: clock_recovery::MM's interpolator bank (clock_recovery/mm.h:173-178): phases x tapsPerPhase
+ * floats, row p = interpBank.phases[p] (multirate/polyphase_bank.h:32-34); returns phases * tapsPerPhase
+ * (out NULL too); phases in [1, SDRGPU_MM_MAX_PHASES], tapsPerPhase in [1, SDRGPU_MM_MAX_TAPS] */
+#define SDRGPU_MM_MAX_PHASES 1024
+#define SDRGPU_MM_MAX_TAPS 64
+int  sdrgpu_mm_interp_bank(int phases, int tapsPerPhase, float* out);
 
 /* --------------------------------------------------------- spectrum ---- */
 /* Window * FFT(N, forward, unnormalised) * 10*log10(|X|^2) of nz <= N samples,
@@ -248,9 +261,77 @@ int sdrgpu_squelch_create(sdrgpu_block** h, int device, double level);
 int sdrgpu_squelch_set_level(sdrgpu_block* h, double level);  /* setLevel (squelch.h:27-31): from the next call */
 int sdrgpu_squelch_get_muted(sdrgpu_block* h, int* muted);    /* state after the last call (synchronises) */
 
+/* ------------------------------------------------ symbol recovery ---- */
+/* The blocks behind WFM's "Decode RDS" (decoder_modules/radio/src/demodulators/wfm.h:56-69) and the
+ * digital demodulators made of them. The loops are serial recurrences run by one workgroup per stream,
+ * every step in the reference's operation order without contraction; state stays on the device between
+ * calls, so results do not depend on how a stream is cut into calls. A setter also takes the handle of
+ * a chain that holds its block (sdrgpu_fast_agc_set / sdrgpu_costas_set_* on a PSK handle: the first
+ * such block; sdrgpu_mm_set_* on a PSK, GFSK or RDS handle: its last block). */
+/* loop::FastAGC<T> (loop/fast_agc.h:13-79); dtype F32 or C64; bit-identical to the reference
+ * arithmetic. _set = setSetPoint / setMaxGain / setRate / setInitGain (:24-46, the gain is kept);
+ * set_gain (:48) is latched and applied at the next call; reset -> initGain (:54) */
+int sdrgpu_fast_agc_create(sdrgpu_block** h, int device, int dtype, double setPoint, double maxGain, double rate, double initGain);
+int sdrgpu_fast_agc_set(sdrgpu_block* h, double setPoint, double maxGain, double rate, double initGain);
+int sdrgpu_fast_agc_set_gain(sdrgpu_block* h, double gain);
+int sdrgpu_fast_agc_get_gain(sdrgpu_block* h, float* gain);    /* (synchronises) */
+/* loop::Costas<ORDER> (loop/costas.h:17-45 over loop/pll.h:15-62, loop/phase_control_loop.h:58-85);
+ * order 2, 4 or 8; C64 -> C64. Arguments in PLL::init's order (pll.h:15); alpha / beta =
+ * criticallyDamped(bandwidth) in float (pll.h:20-22). The phasor is the device libm's cosf / sinf, so
+ * outputs follow the reference within the loop's own sensitivity to the last bit of the phasor
+ * (DESIGN.md 3.3), not bit for bit. reset -> initPhase, initFreq (pll.h:55-62). SDRGPU_EARG: an order
+ * other than 2 / 4 / 8, minFreq >= maxFreq (the reference asserts), a phase or frequency that is not
+ * finite or beyond 1024 rad (the phase wrap is a subtraction loop). */
+int sdrgpu_costas_create(sdrgpu_block** h, int device, int order, double bandwidth, double initPhase, double initFreq,
+                         double minFreq, double maxFreq);
+int sdrgpu_costas_set_bandwidth(sdrgpu_block* h, double bandwidth);                  /* pll.h:27 */
+int sdrgpu_costas_set_freq_limits(sdrgpu_block* h, double minFreq, double maxFreq);   /* pll.h:49: clamps freq at the next call */
+/* clock_recovery::MM<T> (clock_recovery/mm.h:24-156); dtype F32 or C64. Output count and every
+ * output are bit-identical to the reference arithmetic with these definitions / deviations:
+ *  - the interpolator dot product (volk_32f_x2_dot_prod_32f / volk_32fc_32f_dot_prod_32fc, whose SIMD
+ *    variants are unpinned) is VOLK's generic kernel: ascending tap order, fp32, unfused;
+ *  - the T - 1 history samples start as zeros (the reference leaves them uninitialised); reset
+ *    (mm.h:87-98) keeps them, as the reference does;
+ *  - create and the setters refuse (SDRGPU_EARG) parameters with omega * (1 - omegaRelLimit) - muGain
+ *    < 1: with that every output consumes at least one input sample, a call of `count` samples makes
+ *    at most `count` outputs, and sdrgpu_block_out_count(count) returns that CAPACITY (= count), not
+ *    the exact count, for this block and for every chain that ends in it (PSK, GFSK, RDS);
+ *  - the exact count is the call's return value: the kernel writes it to device memory and
+ *    process_dev WAITS for the stream to read it, once, at the end of the call.
+ * set_omega (mm.h:40-50) also zeroes offset and phase; set_gains / set_omega_rel_limit (:52-71) keep
+ * the state. Setters apply at the next call. */
+int sdrgpu_mm_create(sdrgpu_block** h, int device, int dtype, double omega, double omegaGain, double muGain,
+                     double omegaRelLimit, int interpPhases, int interpTaps);
+int sdrgpu_mm_set_omega(sdrgpu_block* h, double omega);
+int sdrgpu_mm_set_gains(sdrgpu_block* h, double omegaGain, double muGain);
+int sdrgpu_mm_set_omega_rel_limit(sdrgpu_block* h, double omegaRelLimit);
+/* digital::BinarySlicer (digital/binary_slicer.h:12-18): F32 -> U8, out = in > 0.0f */
+int sdrgpu_binary_slicer_create(sdrgpu_block** h, int device);
+/* digital::DifferentialDecoder (digital/differential_decoder.h:14-47): U8 -> U8,
+ * out[i] = (in[i] - in[i-1] + modulus) % modulus; the previous call's last symbol is carried */
+int sdrgpu_differential_decoder_create(sdrgpu_block** h, int device, int modulus, int initSym);
+/* demod::PSK<ORDER> (demod/psk.h:25-43, 138-143): FIR(rootRaisedCosine) -> FastAGC(1, 10e6, agcRate)
+ * -> Costas<order>(costasBandwidth) -> MM<complex_t>(samplerate / symbolrate, ...); C64 -> C64 symbols */
+int sdrgpu_psk_create(sdrgpu_block** h, int device, int order, double symbolrate, double samplerate, int rrcTapCount,
+                      double rrcBeta, double agcRate, double costasBandwidth, double omegaGain, double muGain,
+                      double omegaRelLimit);
+/* demod::GFSK (demod/gfsk.h:24-41, 131-135): Quadrature(deviation) -> FIR(rootRaisedCosine) ->
+ * MM<float>; C64 -> F32 soft symbols */
+int sdrgpu_gfsk_create(sdrgpu_block** h, int device, double symbolrate, double samplerate, double deviation, int rrcTapCount,
+                       double rrcBeta, double omegaGain, double muGain, double omegaRelLimit);
+/* WFM's RDS symbol chain with wfm.h:57-68's constants: C64 RDS baseband at 5 kS/s (it may be the device
+ * pointer of sdrgpu_broadcast_fm_rds_dev) -> FastAGC(1, 1e6, 0.1) -> Costas<2>(0.005) -> FIR(bandPass
+ * <complex_t>(0, 2375, 100, 5000)) -> Costas<2>(0.01, 0, w, 0.9 w, 1.1 w), w = hzToRads(2375 / 2, 5000)
+ * -> ComplexToReal -> MM<float>(5000 / 1187.5, 1e-6, 0.01, 0.01) -> BinarySlicer ->
+ * DifferentialDecoder(2); U8 bits out (what rds::RDSDecoder takes). The slicer and the decoder run in
+ * the MM kernel's epilogue; rds_symbols_dev gives the last call's soft symbols (what wfm.h:71-73 feeds
+ * the symbol diagram): device pointer and count, valid until the next call. */
+int sdrgpu_rds_create(sdrgpu_block** h, int device);
+int sdrgpu_rds_symbols_dev(sdrgpu_block* h, const float** out, int* n);
+
 int sdrgpu_block_process(sdrgpu_block* h, const void* in, int count, void* out);      /* host buffers */
 int sdrgpu_block_process_dev(sdrgpu_block* h, const void* in, int count, void* out, void* stream);
-int sdrgpu_block_out_count(sdrgpu_block* h, int count);   /* exact output count of the next call */
+int sdrgpu_block_out_count(sdrgpu_block* h, int count);   /* exact output count of the next call (MM and chains ending in it: the capacity) */
 int sdrgpu_block_reset(sdrgpu_block* h);
 int sdrgpu_block_destroy(sdrgpu_block* h);
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SDRGPU_LIB_PATH: load another build of the same ABI (A/B timing of two builds on one box)
 LIB_PATH = os.environ.get("SDRGPU_LIB_PATH") or os.path.join(_HERE, "lib", "libsdrgpu.so")
 
-F32, C64 = 0, 1
+F32, C64, U8 = 0, 1, 2
 WIN_RECTANGULAR, WIN_HAMMING, WIN_HANN, WIN_BLACKMAN, WIN_NUTTALL, WIN_BH4, WIN_BH7 = range(7)
 CONV_U8, CONV_I16, CONV_I24, CONV_I32, CONV_F64, CONV_I8, CONV_F32 = range(7)
 
@@ -146,6 +146,25 @@ def _load():
         "sdrgpu_squelch_create": (i, [pp, i, d]),
         "sdrgpu_squelch_set_level": (i, [vp, d]),
         "sdrgpu_squelch_get_muted": (i, [vp, ctypes.POINTER(i)]),
+        "sdrgpu_taps_root_raised_cosine": (i, [i, d, d, fp]),
+        "sdrgpu_mm_interp_bank": (i, [i, i, fp]),
+        "sdrgpu_fast_agc_create": (i, [pp, i, i, d, d, d, d]),
+        "sdrgpu_fast_agc_set": (i, [vp, d, d, d, d]),
+        "sdrgpu_fast_agc_set_gain": (i, [vp, d]),
+        "sdrgpu_fast_agc_get_gain": (i, [vp, ctypes.POINTER(ctypes.c_float)]),
+        "sdrgpu_costas_create": (i, [pp, i, i, d, d, d, d, d]),
+        "sdrgpu_costas_set_bandwidth": (i, [vp, d]),
+        "sdrgpu_costas_set_freq_limits": (i, [vp, d, d]),
+        "sdrgpu_mm_create": (i, [pp, i, i, d, d, d, d, i, i]),
+        "sdrgpu_mm_set_omega": (i, [vp, d]),
+        "sdrgpu_mm_set_gains": (i, [vp, d, d]),
+        "sdrgpu_mm_set_omega_rel_limit": (i, [vp, d]),
+        "sdrgpu_binary_slicer_create": (i, [pp, i]),
+        "sdrgpu_differential_decoder_create": (i, [pp, i, i, i]),
+        "sdrgpu_psk_create": (i, [pp, i, i, d, d, i, d, d, d, d, d, d]),
+        "sdrgpu_gfsk_create": (i, [pp, i, d, d, d, i, d, d, d, d]),
+        "sdrgpu_rds_create": (i, [pp, i]),
+        "sdrgpu_rds_symbols_dev": (i, [vp, pp, ctypes.POINTER(i)]),
         "sdrgpu_block_process": (i, [vp, vp, i, vp]),
         "sdrgpu_block_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_block_out_count": (i, [vp, i]),

@@ -26,6 +26,7 @@ SOURCES = [
     ("blocks.hip", []),
     ("channelizer.hip", []),
     ("loops.hip", ["-ffp-contract=off"]),   # bit-exact serial recurrences
+    ("symsync.hip", ["-ffp-contract=off"]),   # bit-exact serial recurrences
     ("ifnr.hip", []),
     ("frontend.hip", []),
     ("consumers.hip", ["-ffp-contract=off"]),   # bit-exact encoders

@@ -1,6 +1,6 @@
 // What the other translation units call in blocks.hip (host side only): chains of blocks and the
-// block constructors (loops.hip), the publication of a new handle and the history carry (loops.hip,
-// channelizer.hip, ifnr.hip), and the hooks through which a spectrum launch carries an RxVFO's stages
+// block constructors (loops.hip, symsync.hip), the publication of a new handle and the history carry (loops.hip,
+// channelizer.hip, ifnr.hip, symsync.hip), and the hooks through which a spectrum launch carries an RxVFO's stages
 // (fft.hip, frontend.hip).
 #pragma once
 #include "sdrgpu_internal.h"
@@ -10,8 +10,26 @@ namespace sdrgpu {
 // ---- composition: a chain of blocks run back to back on one stream ------------------------------
 int chain_new(int dev, int in_dtype, int out_dtype, Block** out);
 int chain_append(Block* chain, Block* kid);   // takes the kid (deleted on error)
+// a freshly built block (its construction's status in rc) joins the chain, or is deleted
+inline int append_owned(Block* chain, Block* b, int rc) {
+    if (rc < 0) { delete b; return rc; }
+    return chain_append(chain, b);
+}
 int chain_size(Block* chain);
 Block* chain_kid(Block* chain, int i);
+// the first (or last) kid of type T of the chain behind h; null where h is no chain or has none
+template <typename T>
+T* find_kid(sdrgpu_block* h, bool last) {
+    if (!h || !h->impl) return nullptr;
+    T* found = nullptr;
+    for (int i = 0, n = chain_size(h->impl); i < n; i++) {
+        if (auto* k = dynamic_cast<T*>(chain_kid(h->impl, i))) {
+            found = k;
+            if (!last) break;
+        }
+    }
+    return found;
+}
 // Constructors: the block is returned even where *rc < 0 (the caller deletes it).
 Block* make_fir_block(int dev, int dtype, int ttype, const float* taps, int n, int decim, bool stereo, int* rc);
 Block* make_xlator_block(int dev, double offsetRad, int* rc);

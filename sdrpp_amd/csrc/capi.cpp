@@ -144,6 +144,12 @@ extern "C" int sdrgpu_taps_band_pass_f(double start, double stop, double transWi
 extern "C" int sdrgpu_taps_band_pass_c(double start, double stop, double transWidth, double sampleRate, int odd, float* out) {
     return taps_band_pass_c(start, stop, transWidth, sampleRate, odd, out);
 }
+extern "C" int sdrgpu_taps_root_raised_cosine(int count, double beta, double Ts, float* out) {
+    return taps_root_raised_cosine(count, beta, Ts, out);
+}
+extern "C" int sdrgpu_mm_interp_bank(int phases, int tapsPerPhase, float* out) {
+    return mm_interp_bank(phases, tapsPerPhase, out);
+}
 extern "C" int sdrgpu_decim_plan(int ratio, int* decims, int* ntaps, const float** taps) {
     return decim_plan(ratio, decims, ntaps, taps);
 }

@@ -126,6 +126,17 @@ int fmif_tables(int bins, float* cr, float* ci, float* ph) {
 }
 
 double hz_to_rads(double f, double fs) { return 2.0 * DB_M_PI * (f / fs); }   // math/hz_to_rads.h
+
+// PhaseControlLoop<float>::criticallyDamped as PLL::init evaluates it (loop/phase_control_loop.h:31-36,
+// loop/pll.h:20-22): T = float, the literals double
+void critically_damped(double bandwidth, float* alpha, float* beta) {
+    const float bw = (float)bandwidth;
+    const float df = (float)(std::sqrt(2.0) / 2.0);
+    const float den = (float)((1.0 + 2.0 * (double)df * (double)bw) + (double)(bw * bw));
+    *alpha = ((float)4 * df * bw) / den;
+    *beta = ((float)4 * bw * bw) / den;
+}
+
 static double sinc(double x) { return (x == 0.0) ? 1.0 : (std::sin(x) / x); } // math/sinc.h
 static int estimate_tap_count(double tw, double fs) { return (int)(3.8 * fs / tw); }  // taps/estimate_tap_count.h
 
@@ -200,6 +211,47 @@ int taps_band_pass_c(double start, double stop, double tw, double fs, int odd, f
         out[2 * i + 1] = pim * (float)corr;
     }
     return count;
+}
+
+// taps::rootRaisedCosine<float> (taps/root_raised_cosine.h:8-29), Ts = samplerate / symbolrate:
+// every tap in fp64 in the reference's order, rounded once
+int taps_root_raised_cosine(int count, double beta, double Ts, float* out) {
+    if (count < 1 || !(beta >= 0.0) || !(Ts > 0.0)) { set_error("root_raised_cosine: bad argument (count %d)", count); return SDRGPU_EARG; }
+    if (!out) return count;
+    static const double DB_M_SQRT2 = 1.4142135623730951;      // dsp/math/constants.h:5
+    double half = (double)count / 2.0;
+    double limit = Ts / (4.0 * beta);
+    for (int i = 0; i < count; i++) {
+        double t = (double)i - half + 0.5;
+        if (t == 0.0) {
+            out[i] = (float)((1.0 + beta * (4.0 / DB_M_PI - 1.0)) / Ts);
+        } else if (t == limit || t == -limit) {
+            out[i] = (float)(((1.0 + 2.0 / DB_M_PI) * std::sin(DB_M_PI / (4.0 * beta)) +
+                              (1.0 - 2.0 / DB_M_PI) * std::cos(DB_M_PI / (4.0 * beta))) * beta / (Ts * DB_M_SQRT2));
+        } else {
+            out[i] = (float)(((std::sin((1.0 - beta) * DB_M_PI * t / Ts) + std::cos((1.0 + beta) * DB_M_PI * t / Ts) * 4.0 * beta * t / Ts) /
+                              ((1.0 - (4.0 * beta * t / Ts) * (4.0 * beta * t / Ts)) * DB_M_PI * t / Ts)) / Ts);
+        }
+    }
+    return count;
+}
+
+// clock_recovery::MM's interpolator bank (mm.h:173-178): windowedSinc(phases * tapsPerPhase,
+// hzToRads(0.5 / phases, 1.0), nuttall, phases) laid out by buildPolyphaseBank
+// (multirate/polyphase_bank.h:32-34): out[p * tapsPerPhase + k] = phases[p][k]
+int mm_interp_bank(int phases, int tapsPerPhase, float* out) {
+    if (phases < 1 || phases > SDRGPU_MM_MAX_PHASES || tapsPerPhase < 1 || tapsPerPhase > SDRGPU_MM_MAX_TAPS) {
+        set_error("mm: interpolator bank %d x %d outside [1, %d] x [1, %d]", phases, tapsPerPhase, SDRGPU_MM_MAX_PHASES,
+                  SDRGPU_MM_MAX_TAPS);
+        return SDRGPU_EARG;
+    }
+    const int total = phases * tapsPerPhase;
+    if (!out) return total;
+    std::vector<float> lp(total);
+    windowed_sinc(total, hz_to_rads(0.5 / (double)phases, 1.0), lp.data(), [](double n, double N) { return nuttall(n, N); },
+                  (double)phases);
+    for (int i = 0; i < total; i++) out[((phases - 1) - (i % phases)) * tapsPerPhase + (i / phases)] = lp[i];
+    return total;
 }
 
 int decim_plan(int ratio, int* decims, int* ntaps, const float** taps) {        // multirate/decim/plans.h

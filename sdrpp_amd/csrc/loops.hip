@@ -267,13 +267,8 @@ struct BroadcastFmBlock : Block {
         pilot.reset(make_fir_block(dev, SDRGPU_C64, SDRGPU_C64, pt.data(), np, 1, false, &rc));
         SDRGPU_CHECK(rc);
         delay = ((np - 1) / 2) + 1;
-        // PLL(25000 / fs, 0, 19 kHz, 18.75 kHz, 19.25 kHz) (broadcast_fm.h:47); criticallyDamped
-        // evaluated as PhaseControlLoop<float> does (phase_control_loop.h:31-36)
-        const float bw = (float)(25000.0 / samplerate);
-        const float df = (float)(std::sqrt(2.0) / 2.0);
-        const float den = (float)((1.0 + 2.0 * (double)df * (double)bw) + (double)(bw * bw));
-        pp.alpha = ((float)4 * df * bw) / den;
-        pp.beta = ((float)4 * bw * bw) / den;
+        // PLL(25000 / fs, 0, 19 kHz, 18.75 kHz, 19.25 kHz) (broadcast_fm.h:47)
+        critically_damped(25000.0 / samplerate, &pp.alpha, &pp.beta);
         pp.minPhase = -3.1415926535f;
         pp.maxPhase = 3.1415926535f;
         pp.phaseDelta = pp.maxPhase - pp.minPhase;
@@ -350,11 +345,6 @@ struct BroadcastFmBlock : Block {
 };
 
 // ---------------------------------------------------------- chain building
-// a freshly built block (its construction's status in rc) joins the chain, or is deleted
-static int append_owned(Block* chain, Block* b, int rc) {
-    if (rc < 0) { delete b; return rc; }
-    return chain_append(chain, b);
-}
 static int append_map(Block* chain, int dev, MapKind kind) {
     auto* m = new MapBlock();
     m->device = dev;
@@ -370,19 +360,6 @@ static AgcBlock* make_demod_agc(int dev, int dtype, double attack, double decay,
     *rc = a->setup(dev, dtype, 1.0, attack, decay, 10e6, 10.0, INFINITY);
     a->p.enabled = enabled ? 1 : 0;
     return a;
-}
-// the first (or last) kid of type T of the chain behind h; null where h is no chain or has none
-template <typename T>
-static T* find_kid(sdrgpu_block* h, bool last) {
-    if (!h || !h->impl) return nullptr;
-    T* found = nullptr;
-    for (int i = 0, n = chain_size(h->impl); i < n; i++) {
-        if (auto* k = dynamic_cast<T*>(chain_kid(h->impl, i))) {
-            found = k;
-            if (!last) break;
-        }
-    }
-    return found;
 }
 // AGC access inside the AM / SSB chains: `which` 0 = the first AGC of the chain (AM carrier
 // AGC in CARRIER mode, the SSB AGC), 1 = the last (AM audio AGC)

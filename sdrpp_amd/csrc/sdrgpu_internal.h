@@ -65,7 +65,7 @@ struct PinnedBuf {
     template <typename T> const T* as_const() const { return reinterpret_cast<const T*>(p); }
 };
 
-inline size_t esize(int dtype) { return dtype == SDRGPU_C64 ? 8 : 4; }
+inline size_t esize(int dtype) { return dtype == SDRGPU_C64 ? 8 : (dtype == SDRGPU_U8 ? 1 : 4); }
 
 // A handle's device state is rewritten by every call (NCO coarse table, history / quadrature
 // ping-pong buffers, FFT scratch), so calls must not overlap. Calls on one stream are ordered by
@@ -103,10 +103,13 @@ int taps_low_pass(double cutoff, double tw, double fs, int odd, float* out);
 int taps_high_pass(double cutoff, double tw, double fs, int odd, float* out);
 int taps_band_pass_f(double start, double stop, double tw, double fs, int odd, float* out);
 int taps_band_pass_c(double start, double stop, double tw, double fs, int odd, float* out);
+int taps_root_raised_cosine(int count, double beta, double Ts, float* out);
+int mm_interp_bank(int phases, int tapsPerPhase, float* out);
 int decim_plan(int ratio, int* decims, int* ntaps, const float** taps);
 int fmif_window(int bins, float* out);
 int fmif_tables(int bins, float* cr, float* ci, float* ph);   // 32 x 32, 32 x 32, 32 x 2 floats
 double hz_to_rads(double f, double fs);
+void critically_damped(double bandwidth, float* alpha, float* beta);   // PLL / Costas loop coefficients
 double xlator_effective_omega(double offsetRad);
 
 // Double-double phase accumulator: keeps (w * n) mod 2pi to ~1e-16 rad over

@@ -480,6 +480,141 @@ class Squelch(Block):
         return bool(m.value)
 
 
+# ---- symbol recovery (include/sdrgpu.h "symbol recovery") -------------------
+def root_raised_cosine(count, beta, Ts):
+    """taps::rootRaisedCosine<float>(count, beta, Ts) (taps/root_raised_cosine.h:8-29); Ts = samplerate / symbolrate."""
+    out = np.empty(check(lib.sdrgpu_taps_root_raised_cosine(int(count), float(beta), float(Ts), None)), np.float32)
+    check(lib.sdrgpu_taps_root_raised_cosine(int(count), float(beta), float(Ts), _fptr(out)))
+    return out
+
+
+def mm_interp_bank(phases=128, taps_per_phase=8):
+    """MM's interpolator bank (clock_recovery/mm.h:173-178): float32 [phases, taps_per_phase] (host only)."""
+    n = check(lib.sdrgpu_mm_interp_bank(int(phases), int(taps_per_phase), None))
+    out = np.empty(n, np.float32)
+    check(lib.sdrgpu_mm_interp_bank(int(phases), int(taps_per_phase), _fptr(out)))
+    return out.reshape(int(phases), int(taps_per_phase))
+
+
+class FastAGC(Block):
+    """dsp::loop::FastAGC<T> (loop/fast_agc.h); bit-exact recurrence."""
+
+    def __init__(self, set_point, max_gain, rate, init_gain=1.0, complex_data=False, device=0):
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_fast_agc_create, device, C64 if complex_data else F32, float(set_point), float(max_gain),
+                  float(rate), float(init_gain))
+        super().__init__(h, npd, npd)
+
+    def set(self, set_point, max_gain, rate, init_gain=1.0):
+        """setSetPoint / setMaxGain / setRate / setInitGain (fast_agc.h:24-46): the gain is kept."""
+        check(lib.sdrgpu_fast_agc_set(self._h, float(set_point), float(max_gain), float(rate), float(init_gain)))
+
+    def set_gain(self, gain):
+        check(lib.sdrgpu_fast_agc_set_gain(self._h, float(gain)))
+
+    def get_gain(self):
+        g = ctypes.c_float()
+        check(lib.sdrgpu_fast_agc_get_gain(self._h, ctypes.byref(g)))
+        return g.value
+
+
+class Costas(Block):
+    """dsp::loop::Costas<ORDER> (loop/costas.h); arguments in PLL::init's order (loop/pll.h:15)."""
+
+    def __init__(self, order, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-float(np.float32(3.1415926535)),
+                 max_freq=float(np.float32(3.1415926535)), device=0):
+        h = _make(lib.sdrgpu_costas_create, device, int(order), float(bandwidth), float(init_phase), float(init_freq),
+                  float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+    def set_bandwidth(self, bandwidth):
+        check(lib.sdrgpu_costas_set_bandwidth(self._h, float(bandwidth)))
+
+    def set_freq_limits(self, min_freq, max_freq):
+        check(lib.sdrgpu_costas_set_freq_limits(self._h, float(min_freq), float(max_freq)))
+
+
+class _MMSetters:
+    """The MM setters (clock_recovery/mm.h:40-71), on an MM or on a chain that ends in one."""
+
+    def set_omega(self, omega):
+        check(lib.sdrgpu_mm_set_omega(self._h, float(omega)))
+
+    def set_gains(self, omega_gain, mu_gain):
+        check(lib.sdrgpu_mm_set_gains(self._h, float(omega_gain), float(mu_gain)))
+
+    def set_omega_rel_limit(self, rel):
+        check(lib.sdrgpu_mm_set_omega_rel_limit(self._h, float(rel)))
+
+
+class MM(Block, _MMSetters):
+    """dsp::clock_recovery::MM<T> (clock_recovery/mm.h). ``out_count`` is the capacity (= count);
+    ``process`` / ``process_dev`` return the exact count (process_dev waits for the stream)."""
+
+    def __init__(self, omega, omega_gain, mu_gain, omega_rel_limit, interp_phases=128, interp_taps=8, complex_data=False,
+                 device=0):
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_mm_create, device, C64 if complex_data else F32, float(omega), float(omega_gain), float(mu_gain),
+                  float(omega_rel_limit), int(interp_phases), int(interp_taps))
+        super().__init__(h, npd, npd)
+
+
+class BinarySlicer(Block):
+    """dsp::digital::BinarySlicer (digital/binary_slicer.h): float32 -> uint8."""
+
+    def __init__(self, device=0):
+        super().__init__(_make(lib.sdrgpu_binary_slicer_create, device), np.float32, np.uint8)
+
+
+class DifferentialDecoder(Block):
+    """dsp::digital::DifferentialDecoder (digital/differential_decoder.h): uint8 -> uint8."""
+
+    def __init__(self, modulus, init_sym=0, device=0):
+        super().__init__(_make(lib.sdrgpu_differential_decoder_create, device, int(modulus), int(init_sym)), np.uint8, np.uint8)
+
+
+class PSK(Block, _MMSetters):
+    """dsp::demod::PSK<ORDER> (demod/psk.h): complex64 samples -> complex64 symbols."""
+
+    def __init__(self, order, symbolrate, samplerate, rrc_taps, rrc_beta, agc_rate, costas_bandwidth, omega_gain, mu_gain,
+                 omega_rel_limit=0.01, device=0):
+        h = _make(lib.sdrgpu_psk_create, device, int(order), float(symbolrate), float(samplerate), int(rrc_taps), float(rrc_beta),
+                  float(agc_rate), float(costas_bandwidth), float(omega_gain), float(mu_gain), float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class GFSK(Block, _MMSetters):
+    """dsp::demod::GFSK (demod/gfsk.h): complex64 samples -> float32 soft symbols."""
+
+    def __init__(self, symbolrate, samplerate, deviation, rrc_taps, rrc_beta, omega_gain, mu_gain, omega_rel_limit=0.01,
+                 device=0):
+        h = _make(lib.sdrgpu_gfsk_create, device, float(symbolrate), float(samplerate), float(deviation), int(rrc_taps),
+                  float(rrc_beta), float(omega_gain), float(mu_gain), float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.float32)
+
+
+class RDSBits(Block):
+    """WFM's RDS symbol chain (radio module, demodulators/wfm.h:57-68): complex64 RDS baseband at
+    5 kS/s (``BroadcastFM.rds_output()``, or its device pointer through ``process_dev``) -> uint8
+    differentially decoded bits; ``symbols()`` is the last call's soft symbols."""
+
+    def __init__(self, device=0):
+        super().__init__(_make(lib.sdrgpu_rds_create, device), np.complex64, np.uint8)
+
+    def symbols_dev(self):
+        """(device pointer, count) of the last call's soft symbols."""
+        ptr, n = ctypes.c_void_p(), ctypes.c_int()
+        check(lib.sdrgpu_rds_symbols_dev(self._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return ptr.value, n.value
+
+    def symbols(self):
+        ptr, n = self.symbols_dev()
+        out = np.empty(n, np.float32)
+        if n:
+            check(lib.sdrgpu_memcpy_d2h(_fptr(out), _vp(ptr), out.nbytes, None))
+        return out
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
