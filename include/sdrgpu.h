@@ -335,6 +335,63 @@ int sdrgpu_block_out_count(sdrgpu_block* h, int count);   /* exact output count 
 int sdrgpu_block_reset(sdrgpu_block* h);
 int sdrgpu_block_destroy(sdrgpu_block* h);
 
+/* ---------------------------------------------------- stream banks ---- */
+/* A bank is S independent streams that share one set of parameters, each with its own state: element
+ * m of stream k is x[m * S + k], the layout sdrgpu_channelizer writes (out[m * M + k], S = M), so a
+ * channelizer's device output feeds a bank as it is. Outputs have the same layout. A call processes
+ * `frames` rows; state and history stay on the device, and results do not depend on how the rows are
+ * cut into calls. The loops (FastAGC, Costas, MM) run one lane per stream, 64 streams per wave, on the
+ * per-sample steps of the single-stream kernels: every column is bit-identical to the single-stream
+ * block fed that column. Parameters are fixed at creation.
+ * Every create function takes (handle, device, streams, the arguments of the single-stream create
+ * function in its order) and applies that function's checks; streams < 1 is SDRGPU_EARG. All checks run
+ * before the device is selected. frames * streams beyond INT_MAX (the kernels' index type) is
+ * SDRGPU_EARG at the call, streams beyond INT_MAX / 64 (state words and history rows) at create. */
+typedef struct sdrgpu_bank sdrgpu_bank;
+/* demod::Quadrature per stream (demod/quadrature.h:41-56); C64 -> F32; every stream's previous sample is
+ * 0 after create / reset */
+int sdrgpu_bank_quadrature_create(sdrgpu_bank** h, int device, int streams, double deviationRad);
+/* filter::FIR<D, float> per stream (filter/fir.h:60-80): real taps shared by all streams, dtype F32 or
+ * C64, no decimation; out[m*S + k] = sum_j buf_k[m + j] * taps[j] over [ntaps - 1 history rows || new],
+ * taps not reversed, summed in ascending tap order in fp32 without contraction (not bit-identical to
+ * sdrgpu_fir_create, whose kernel and summation order depend on the shape); history zero at create / reset */
+int sdrgpu_bank_fir_create(sdrgpu_bank** h, int device, int streams, int dtype, const float* taps, int ntaps);
+/* loop::FastAGC<T> per stream (loop/fast_agc.h:13-79); reset -> initGain */
+int sdrgpu_bank_fast_agc_create(sdrgpu_bank** h, int device, int streams, int dtype, double setPoint, double maxGain, double rate,
+                                double initGain);
+/* loop::Costas<ORDER> per stream (loop/costas.h:17-45 over loop/pll.h:15-62, loop/phase_control_loop.h:58-85);
+ * the refusals of sdrgpu_costas_create; bit-identical to it on the same device */
+int sdrgpu_bank_costas_create(sdrgpu_bank** h, int device, int streams, int order, double bandwidth, double initPhase,
+                              double initFreq, double minFreq, double maxFreq);
+/* clock_recovery::MM<T> per stream (clock_recovery/mm.h:24-156) with the definitions, deviations and
+ * refusals of sdrgpu_mm_create. The output counts depend on the data and differ per stream: output j of
+ * stream k is out[j*S + k] for j < counts[k]; the elements of a row past a stream's count are left as
+ * they were. sdrgpu_bank_out_rows(frames) = frames is the capacity; the call WAITS for its stream once,
+ * at the end, and returns the largest per-stream count (the rows that hold anything). reset keeps the
+ * (T - 1) x S history (mm.h:87-98). */
+int sdrgpu_bank_mm_create(sdrgpu_bank** h, int device, int streams, int dtype, double omega, double omegaGain, double muGain,
+                          double omegaRelLimit, int interpPhases, int interpTaps);
+/* demod::PSK<ORDER> per stream (demod/psk.h:25-43, 138-143): bank FIR(rootRaisedCosine) -> bank
+ * FastAGC(1, 10e6, agcRate) -> bank Costas<order> -> bank MM<complex_t>, the constants of
+ * sdrgpu_psk_create; bit-identical to those banks run one after another; counts as the MM bank */
+int sdrgpu_bank_psk_create(sdrgpu_bank** h, int device, int streams, int order, double symbolrate, double samplerate,
+                           int rrcTapCount, double rrcBeta, double agcRate, double costasBandwidth, double omegaGain,
+                           double muGain, double omegaRelLimit);
+/* demod::GFSK per stream (demod/gfsk.h:24-41, 131-135): bank Quadrature(deviation) -> bank
+ * FIR(rootRaisedCosine) -> bank MM<float>; C64 -> F32 soft symbols */
+int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate, double deviation,
+                            int rrcTapCount, double rrcBeta, double omegaGain, double muGain, double omegaRelLimit);
+
+/* device buffers of frames * S (in) and sdrgpu_bank_out_rows(frames) * S (out) elements, on `stream` (0:
+ * the handle's own); asynchronous except for a bank that ends in MM (above). Returns the rows written. */
+int sdrgpu_bank_process_dev(sdrgpu_bank* h, const void* in, int frames, void* out, void* stream);
+int sdrgpu_bank_process(sdrgpu_bank* h, const void* in, int frames, void* out);   /* host buffers (synchronous) */
+int sdrgpu_bank_out_rows(sdrgpu_bank* h, int frames);     /* row capacity of the next call of `frames` rows */
+int sdrgpu_bank_out_counts(sdrgpu_bank* h, int* counts);  /* counts[S]: per-stream outputs of the last call (synchronises) */
+int sdrgpu_bank_streams(sdrgpu_bank* h);
+int sdrgpu_bank_reset(sdrgpu_bank* h);
+int sdrgpu_bank_destroy(sdrgpu_bank* h);
+
 /* ------------------------------------------------- device IQ front end ---- */
 /* IQFrontEnd's data path on the device (signal_path/iq_frontend.cpp:15-52, 115-249; SURVEY
  * 8f rank 1): ingest conversion -> [PowerDecimator] -> [DCBlocker] -> [Conjugate] -> VFOs

@@ -165,6 +165,20 @@ def _load():
         "sdrgpu_gfsk_create": (i, [pp, i, d, d, d, i, d, d, d, d]),
         "sdrgpu_rds_create": (i, [pp, i]),
         "sdrgpu_rds_symbols_dev": (i, [vp, pp, ctypes.POINTER(i)]),
+        "sdrgpu_bank_quadrature_create": (i, [pp, i, i, d]),
+        "sdrgpu_bank_fir_create": (i, [pp, i, i, i, fp, i]),
+        "sdrgpu_bank_fast_agc_create": (i, [pp, i, i, i, d, d, d, d]),
+        "sdrgpu_bank_costas_create": (i, [pp, i, i, i, d, d, d, d, d]),
+        "sdrgpu_bank_mm_create": (i, [pp, i, i, i, d, d, d, d, i, i]),
+        "sdrgpu_bank_psk_create": (i, [pp, i, i, i, d, d, i, d, d, d, d, d, d]),
+        "sdrgpu_bank_gfsk_create": (i, [pp, i, i, d, d, d, i, d, d, d, d]),
+        "sdrgpu_bank_process_dev": (i, [vp, vp, i, vp, vp]),
+        "sdrgpu_bank_process": (i, [vp, vp, i, vp]),
+        "sdrgpu_bank_out_rows": (i, [vp, i]),
+        "sdrgpu_bank_out_counts": (i, [vp, ctypes.POINTER(i)]),
+        "sdrgpu_bank_streams": (i, [vp]),
+        "sdrgpu_bank_reset": (i, [vp]),
+        "sdrgpu_bank_destroy": (i, [vp]),
         "sdrgpu_block_process": (i, [vp, vp, i, vp]),
         "sdrgpu_block_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_block_out_count": (i, [vp, i]),

@@ -27,6 +27,7 @@ SOURCES = [
     ("channelizer.hip", []),
     ("loops.hip", ["-ffp-contract=off"]),   # bit-exact serial recurrences
     ("symsync.hip", ["-ffp-contract=off"]),   # bit-exact serial recurrences
+    ("bank.hip", ["-ffp-contract=off"]),   # bit-exact serial recurrences, one lane per stream
     ("ifnr.hip", []),
     ("frontend.hip", []),
     ("consumers.hip", ["-ffp-contract=off"]),   # bit-exact encoders

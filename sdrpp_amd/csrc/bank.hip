@@ -1,0 +1,503 @@
+// Host side of the stream banks (the kernels, the layout and the kernel form are in bank_kernels.h, which
+// also says why this file is built with -ffp-contract=off): S independent streams with shared
+// parameters, element m of stream k at x[m * S + k], one launch per block and call.
+//   BankQuad, BankFir        demod::Quadrature, filter::FIR<D, float> per stream
+//   BankFastAgc, BankCostas, BankMm   loop::FastAGC<T>, loop::Costas<ORDER>, clock_recovery::MM<T> per stream
+//   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip)
+// Top to bottom: the Bank base and its handle, the blocks (each: configure = the argument checks and the
+// parameters, host only; init = device state; reset; run = its launch), the C entry points.
+// A create function checks every argument (configure, of a chain: of all its stages) before it selects
+// the device. Banks are not Blocks: sdrgpu_block_process sizes its buffers as count * esize and knows
+// nothing of rows.
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <memory>
+#include <vector>
+#include "sdrgpu_internal.h"
+#include "bank_kernels.h"
+#include "blocks.h"
+#include "symsync_args.h"
+
+namespace sdrgpu {
+
+struct Bank {
+    int device = 0, S = 1;
+    int in_dtype = SDRGPU_C64, out_dtype = SDRGPU_C64;
+    hipStream_t own = nullptr;   // the handle's own stream (a chain's stages have none)
+    StreamOrder order;           // entry points only, as Block::order
+    PinnedBuf pin_in, pin_out;
+    DevBuf dev_in, dev_out;
+    int lastRows = 0;
+    virtual ~Bank() {
+        if (own) (void)hipStreamDestroy(own);
+    }
+    // device state (allocations, uploads, reset); the device is selected
+    virtual int init() = 0;
+    virtual int reset() = 0;
+    // frames rows at `in` -> rows at `out`, asynchronous on s unless the block says otherwise; returns the rows
+    virtual int run(const void* in, int frames, void* out, hipStream_t s) = 0;
+    // data-dependent per-stream counts (MM): rows past a stream's count keep what `out` held
+    virtual bool ragged() const { return false; }
+    virtual void counts(int* c) const { std::fill(c, c + S, lastRows); }
+    // streams and the index bounds of the kernels: state words f * S + k (MMW_WORDS) and history rows
+    // (up to SDRGPU_MM_MAX_TAPS - 1) are int
+    static bool streams_ok(int streams) {
+        if (streams < 1 || streams > INT_MAX / 64) { set_error("bank: %d streams outside [1, %d]", streams, INT_MAX / 64); return false; }
+        return true;
+    }
+    bool frames_ok(int frames) const {
+        if (frames < 0 || (long long)frames * S > INT_MAX) {
+            set_error("bank: %d frames of %d streams do not fit the kernels' int index", frames, S);
+            return false;
+        }
+        return true;
+    }
+};
+
+// a state buffer's initial words, uploaded on the null stream (the entry point synchronises: blocks.h)
+template <typename T>
+static int upload(DevBuf& b, const std::vector<T>& v) {
+    SDRGPU_CHECK(b.ensure(sizeof(T) * v.size()));
+    SDRGPU_HIP(hipMemcpy(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
+    return SDRGPU_OK;
+}
+static dim3 waves_of(int S) { return dim3((S + BANK_W - 1) / BANK_W); }   // one wave per 64 streams, none idle
+
+// ------------------------------------------------------------------ Quadrature
+struct BankQuad : Bank {
+    float invDev = 1.0f;
+    DevBuf prev[2];   // the streams' last samples: [cur] read by the next call, [cur ^ 1] written by it
+    int cur = 0;
+    int configure(int streams, double deviationRad) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = SDRGPU_C64;
+        out_dtype = SDRGPU_F32;
+        invDev = (float)(1.0 / deviationRad);
+        return SDRGPU_OK;
+    }
+    int init() override {
+        for (auto& b : prev) SDRGPU_CHECK(b.ensure(sizeof(float2) * S));
+        return reset();
+    }
+    int reset() override {
+        SDRGPU_HIP(hipMemset(prev[cur].p, 0, sizeof(float2) * S));
+        return SDRGPU_OK;
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int n = frames * S;
+        hipLaunchKernelGGL(bank_quad_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float2*)in, (float*)out, n, S,
+                           prev[cur].as<float2>(), prev[cur ^ 1].as<float2>(), invDev);
+        SDRGPU_HIP(hipGetLastError());
+        cur ^= 1;
+        return frames;
+    }
+};
+
+// ------------------------------------------------------------------------- FIR
+struct BankFir : Bank {
+    std::vector<float> taps;
+    DevBuf tapsDev, hist[2];
+    int cur = 0;
+    int configure(int streams, int dtype, const float* t, int ntaps) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype) || !t || ntaps < 1 || (long long)(ntaps - 1) * streams > INT_MAX) {
+            set_error("bank_fir: dtype %d not F32 / C64, no taps, or %d taps of %d streams beyond the int index", dtype, ntaps, streams);
+            return SDRGPU_EARG;
+        }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        taps.assign(t, t + ntaps);
+        return SDRGPU_OK;
+    }
+    int HS() const { return ((int)taps.size() - 1) * S; }
+    int init() override {
+        SDRGPU_CHECK(upload(tapsDev, taps));
+        for (auto& b : hist) SDRGPU_CHECK(b.ensure(esize(in_dtype) * (size_t)std::max(HS(), 1)));
+        return reset();
+    }
+    int reset() override {
+        SDRGPU_HIP(hipMemset(hist[cur].p, 0, hist[cur].bytes));
+        return SDRGPU_OK;
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int n = frames * S, T = (int)taps.size();
+        if (in_dtype == SDRGPU_C64)
+            hipLaunchKernelGGL(bank_fir_kernel<float2>, dim3((n + 255) / 256), dim3(256), 0, s, (const float2*)in, (float2*)out, n, S,
+                               HS(), tapsDev.as<float>(), T, hist[cur].as<float2>());
+        else
+            hipLaunchKernelGGL(bank_fir_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)in, (float*)out, n, S,
+                               HS(), tapsDev.as<float>(), T, hist[cur].as<float>());
+        SDRGPU_HIP(hipGetLastError());
+        if (HS() > 0) {
+            SDRGPU_CHECK(carry_history(in_dtype, nullptr, hist[cur], in, hist[cur ^ 1], HS(), n, s));
+            cur ^= 1;
+        }
+        return frames;
+    }
+};
+
+// --------------------------------------------------------------------- FastAGC
+struct BankFastAgc : Bank {
+    FastAgcParams p{};
+    float initGain = 1.0f;
+    DevBuf state;   // gain[S]
+    int configure(int streams, int dtype, double setPoint, double maxGain, double rate, double initGain_) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype)) { set_error("bank_fast_agc: dtype %d not F32 / C64", dtype); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        fast_agc_params(p, setPoint, maxGain, rate);
+        initGain = (float)initGain_;
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override { return upload(state, std::vector<float>(S, initGain)); }   // fast_agc.h:54-58
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        if (in_dtype == SDRGPU_C64)
+            hipLaunchKernelGGL(bank_fast_agc_kernel<float2>, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S, p,
+                               state.as<float>());
+        else
+            hipLaunchKernelGGL(bank_fast_agc_kernel<float>, waves_of(S), dim3(BANK_W), 0, s, (const float*)in, (float*)out, frames, S, p,
+                               state.as<float>());
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// ---------------------------------------------------------------------- Costas
+struct BankCostas : Bank {
+    int order = 2;
+    PclParams p{};
+    float initPhase = 0.0f, initFreq = 0.0f;
+    DevBuf state;   // phase[S], freq[S]
+    int configure(int streams, int order_, double bandwidth, double initPhase_, double initFreq_, double minFreq, double maxFreq) {
+        if (!streams_ok(streams) || !costas_args_ok(order_, bandwidth, initPhase_, initFreq_, minFreq, maxFreq)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = out_dtype = SDRGPU_C64;
+        order = order_;
+        critically_damped(bandwidth, &p.alpha, &p.beta);
+        p.minFreq = (float)minFreq;
+        p.maxFreq = (float)maxFreq;
+        initPhase = (float)initPhase_;
+        initFreq = (float)initFreq_;
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override {   // pll.h:55-62
+        std::vector<float> st(2 * (size_t)S, initPhase);
+        std::fill(st.begin() + S, st.end(), initFreq);
+        return upload(state, st);
+    }
+    template <int ORDER>
+    void run_t(const void* in, int frames, void* out, hipStream_t s) {
+        hipLaunchKernelGGL(bank_costas_kernel<ORDER>, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S, p,
+                           state.as<float>());
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        if (order == 2) run_t<2>(in, frames, out, s);
+        else if (order == 4) run_t<4>(in, frames, out, s);
+        else run_t<8>(in, frames, out, s);
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// -------------------------------------------------------------------------- MM
+struct BankMm : Bank {
+    MmParams p{};
+    double omega = 0.0;
+    std::vector<float> interp;
+    DevBuf state, hist, interpDev;   // MMW_WORDS x S words; (T - 1) x S elements; P x T floats
+    PinnedBuf countBuf;              // the call's per-stream counts, read back at the end of run()
+    std::vector<int> last;           // ... and kept for sdrgpu_bank_out_counts
+    int configure(int streams, int dtype, double omega_, double omegaGain, double muGain, double rel, int P, int T) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype)) { set_error("bank_mm: dtype %d not F32 / C64", dtype); return SDRGPU_EARG; }
+        if (!mm_args_ok(omega_, omegaGain, muGain, rel, P, T)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        omega = omega_;
+        mm_pcl_params(p, omega, omegaGain, muGain, rel);
+        p.P = P;
+        p.T = T;
+        p.inStride = 1;
+        p.modulus = 2;
+        interp.resize((size_t)P * T);
+        SDRGPU_CHECK(mm_interp_bank(P, T, interp.data()));
+        last.assign(S, 0);
+        return SDRGPU_OK;
+    }
+    bool ragged() const override { return true; }
+    void counts(int* c) const override { std::copy(last.begin(), last.end(), c); }
+    size_t lds_bytes() const {
+        const size_t tile = (size_t)(BANK_F + p.T - 1) * BANK_W * esize(in_dtype);
+        return tile + (p.P * p.T <= MM_LDS_BANK ? sizeof(float) * interp.size() : 0);
+    }
+    int init() override {
+        SDRGPU_CHECK(upload(interpDev, interp));
+        SDRGPU_CHECK(hist.ensure(esize(in_dtype) * (size_t)std::max((p.T - 1) * S, 1)));
+        SDRGPU_CHECK(countBuf.ensure(sizeof(int) * S));
+        SDRGPU_HIP(hipMemset(hist.p, 0, hist.bytes));   // (the reference's work buffer starts uninitialised)
+        return reset();
+    }
+    int reset() override {   // mm.h:87-98: the state, not the history
+        std::vector<int> st((size_t)MMW_WORDS * S, 0);
+        const float f = (float)omega;
+        int fbits;
+        std::memcpy(&fbits, &f, sizeof(f));
+        std::fill(st.begin() + (size_t)MMW_FREQ * S, st.begin() + (size_t)(MMW_FREQ + 1) * S, fbits);
+        std::fill(last.begin(), last.end(), 0);
+        return upload(state, st);
+    }
+    // as MmBlock::run: the data-dependent counts are the one wait of the call; returns the largest
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        std::fill(last.begin(), last.end(), 0);
+        if (frames == 0) return 0;
+        if (in_dtype == SDRGPU_C64)
+            hipLaunchKernelGGL(bank_mm_kernel<float2>, waves_of(S), dim3(BANK_W), lds_bytes(), s, (const float2*)in, frames, S, (float2*)out,
+                               p, interpDev.as<float>(), hist.as<float2>(), state.as<int>());
+        else
+            hipLaunchKernelGGL(bank_mm_kernel<float>, waves_of(S), dim3(BANK_W), lds_bytes(), s, (const float*)in, frames, S, (float*)out, p,
+                               interpDev.as<float>(), hist.as<float>(), state.as<int>());
+        SDRGPU_HIP(hipGetLastError());
+        SDRGPU_HIP(hipMemcpyAsync(countBuf.p, state.as<int>() + (size_t)MMW_COUNT * S, sizeof(int) * S, hipMemcpyDeviceToHost, s));
+        SDRGPU_HIP(hipStreamSynchronize(s));
+        const int* c = reinterpret_cast<const int*>(countBuf.p);
+        last.assign(c, c + S);
+        return *std::max_element(last.begin(), last.end());
+    }
+};
+
+// ------------------------------------------------- composites: stages back to back
+// Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers of
+// frames * S elements (sized for C64), which grow on demand.
+struct BankChain : Bank {
+    std::vector<std::unique_ptr<Bank>> kids;
+    DevBuf buf[2];
+    // a configured stage joins (rc: its configure's status)
+    int add(Bank* b, int rc) {
+        std::unique_ptr<Bank> k(b);
+        if (rc < 0) return rc;
+        k->device = device;
+        kids.push_back(std::move(k));
+        return SDRGPU_OK;
+    }
+    int init() override {
+        for (auto& k : kids) SDRGPU_CHECK(k->init());
+        return SDRGPU_OK;
+    }
+    int reset() override {
+        for (auto& k : kids) SDRGPU_CHECK(k->reset());
+        return SDRGPU_OK;
+    }
+    bool ragged() const override { return kids.back()->ragged(); }
+    void counts(int* c) const override { kids.back()->counts(c); }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (kids.size() > 1)
+            for (auto& b : buf) SDRGPU_CHECK(b.ensure((size_t)std::max(frames, 1) * S * esize(SDRGPU_C64)));
+        const void* cur = in;
+        int rows = frames;
+        for (size_t i = 0; i < kids.size(); i++) {
+            void* dst = i + 1 == kids.size() ? out : buf[i & 1].p;
+            rows = kids[i]->run(cur, rows, dst, s);
+            if (rows < 0) return rows;
+            kids[i]->lastRows = rows;
+            cur = dst;
+        }
+        return rows;
+    }
+};
+
+// FIR<T, float>(rootRaisedCosine<float>(count, beta, symbolrate, samplerate)) (psk.h:31-32, gfsk.h:32-33)
+static int configure_rrc(BankFir* f, int streams, int dtype, int count, double beta, double symbolrate, double samplerate) {
+    std::vector<float> t;
+    SDRGPU_CHECK(design_taps(t, taps_root_raised_cosine, count, beta, samplerate / symbolrate));
+    return f->configure(streams, dtype, t.data(), (int)t.size());
+}
+
+}  // namespace sdrgpu
+
+struct sdrgpu_bank {
+    sdrgpu::Bank* impl;
+};
+
+using namespace sdrgpu;
+
+// The one way a create function hands a new bank to its caller: rc is the status of configure (every
+// argument check, nothing on the device yet); then the device, the handle's stream and the device
+// state, and the synchronise that publish_block (blocks.h) explains.
+static int publish_bank(sdrgpu_bank** h, Bank* b, int device, int rc) {
+    std::unique_ptr<Bank> own(b);
+    if (rc < 0) return rc;
+    b->device = device;
+    SDRGPU_SET_DEVICE(device);
+    SDRGPU_HIP(hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking));
+    SDRGPU_CHECK(b->init());
+    SDRGPU_HIP(hipDeviceSynchronize());
+    *h = new sdrgpu_bank{own.release()};
+    return SDRGPU_OK;
+}
+
+#define NEED_BANK(h) do { if (!(h) || !(h)->impl) { set_error("null bank handle"); return SDRGPU_EARG; } } while (0)
+#define NEED_BANK_OUT(h, what) do { if (!(h)) { set_error(what ": null handle pointer"); return SDRGPU_EARG; } } while (0)
+
+// ------------------------------------------------------------------- C ABI
+extern "C" int sdrgpu_bank_quadrature_create(sdrgpu_bank** h, int device, int streams, double deviationRad) {
+    NEED_BANK_OUT(h, "bank_quadrature_create");
+    auto* q = new BankQuad();
+    return publish_bank(h, q, device, q->configure(streams, deviationRad));
+}
+extern "C" int sdrgpu_bank_fir_create(sdrgpu_bank** h, int device, int streams, int dtype, const float* taps, int ntaps) {
+    NEED_BANK_OUT(h, "bank_fir_create");
+    auto* f = new BankFir();
+    return publish_bank(h, f, device, f->configure(streams, dtype, taps, ntaps));
+}
+extern "C" int sdrgpu_bank_fast_agc_create(sdrgpu_bank** h, int device, int streams, int dtype, double setPoint, double maxGain,
+                                           double rate, double initGain) {
+    NEED_BANK_OUT(h, "bank_fast_agc_create");
+    auto* a = new BankFastAgc();
+    return publish_bank(h, a, device, a->configure(streams, dtype, setPoint, maxGain, rate, initGain));
+}
+extern "C" int sdrgpu_bank_costas_create(sdrgpu_bank** h, int device, int streams, int order, double bandwidth, double initPhase,
+                                         double initFreq, double minFreq, double maxFreq) {
+    NEED_BANK_OUT(h, "bank_costas_create");
+    auto* c = new BankCostas();
+    return publish_bank(h, c, device, c->configure(streams, order, bandwidth, initPhase, initFreq, minFreq, maxFreq));
+}
+extern "C" int sdrgpu_bank_mm_create(sdrgpu_bank** h, int device, int streams, int dtype, double omega, double omegaGain,
+                                     double muGain, double omegaRelLimit, int interpPhases, int interpTaps) {
+    NEED_BANK_OUT(h, "bank_mm_create");
+    auto* m = new BankMm();
+    return publish_bank(h, m, device, m->configure(streams, dtype, omega, omegaGain, muGain, omegaRelLimit, interpPhases, interpTaps));
+}
+
+// the stages and constants of sdrgpu_psk_create (symsync.hip)
+extern "C" int sdrgpu_bank_psk_create(sdrgpu_bank** h, int device, int streams, int order, double symbolrate, double samplerate,
+                                      int rrcTapCount, double rrcBeta, double agcRate, double costasBandwidth, double omegaGain,
+                                      double muGain, double omegaRelLimit) {
+    NEED_BANK_OUT(h, "bank_psk_create");
+    auto* c = new BankChain();
+    int rc = SDRGPU_OK;
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    else if (!(symbolrate > 0) || !(samplerate > 0)) { set_error("bank_psk_create: bad argument"); rc = SDRGPU_EARG; }
+    c->S = std::max(streams, 1);
+    c->in_dtype = c->out_dtype = SDRGPU_C64;
+    if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, configure_rrc(f, streams, SDRGPU_C64, rrcTapCount, rrcBeta, symbolrate, samplerate)); }
+    if (rc >= 0) { auto* a = new BankFastAgc(); rc = c->add(a, a->configure(streams, SDRGPU_C64, 1.0, 10e6, agcRate, 1.0)); }
+    const double PI = 3.1415926535f;   // FL_M_PI, the default frequency limits (pll.h:15)
+    if (rc >= 0) { auto* l = new BankCostas(); rc = c->add(l, l->configure(streams, order, costasBandwidth, 0.0, 0.0, -PI, PI)); }
+    if (rc >= 0) {
+        auto* m = new BankMm();
+        rc = c->add(m, m->configure(streams, SDRGPU_C64, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8));
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+// the stages and constants of sdrgpu_gfsk_create (symsync.hip)
+extern "C" int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate, double deviation,
+                                       int rrcTapCount, double rrcBeta, double omegaGain, double muGain, double omegaRelLimit) {
+    NEED_BANK_OUT(h, "bank_gfsk_create");
+    auto* c = new BankChain();
+    int rc = SDRGPU_OK;
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    else if (!(symbolrate > 0) || !(samplerate > 0)) { set_error("bank_gfsk_create: bad argument"); rc = SDRGPU_EARG; }
+    c->S = std::max(streams, 1);
+    c->in_dtype = SDRGPU_C64;
+    c->out_dtype = SDRGPU_F32;
+    if (rc >= 0) { auto* q = new BankQuad(); rc = c->add(q, q->configure(streams, hz_to_rads(deviation, samplerate))); }
+    if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, configure_rrc(f, streams, SDRGPU_F32, rrcTapCount, rrcBeta, symbolrate, samplerate)); }
+    if (rc >= 0) {
+        auto* m = new BankMm();
+        rc = c->add(m, m->configure(streams, SDRGPU_F32, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8));
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+extern "C" int sdrgpu_bank_streams(sdrgpu_bank* h) {
+    NEED_BANK(h);
+    return h->impl->S;
+}
+
+extern "C" int sdrgpu_bank_out_rows(sdrgpu_bank* h, int frames) {
+    NEED_BANK(h);
+    return h->impl->frames_ok(frames) ? frames : SDRGPU_EARG;
+}
+
+extern "C" int sdrgpu_bank_process_dev(sdrgpu_bank* h, const void* in, int frames, void* out, void* stream) {
+    NEED_BANK(h);
+    Bank* b = h->impl;
+    if (!b->frames_ok(frames)) return SDRGPU_EARG;
+    if (frames > 0 && (!in || !out)) { set_error("bank_process: bad buffers"); return SDRGPU_EARG; }
+    const hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    SDRGPU_SET_DEVICE(b->device);
+    SDRGPU_CHECK(b->order.follow(s));
+    OrderScope od(b->order, s);
+    const int rows = b->run(in, frames, out, s);
+    if (rows >= 0) b->lastRows = rows;
+    return rows;
+}
+
+// Host buffers through the handle's pinned staging. A bank with data-dependent counts leaves the
+// elements past a stream's count as they were: its device rows start as a copy of the caller's `out`.
+extern "C" int sdrgpu_bank_process(sdrgpu_bank* h, const void* in, int frames, void* out) {
+    NEED_BANK(h);
+    Bank* b = h->impl;
+    if (!b->frames_ok(frames)) return SDRGPU_EARG;
+    if (frames > 0 && (!in || !out)) { set_error("bank_process: bad buffers"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(b->device);
+    const size_t inB = (size_t)frames * b->S * esize(b->in_dtype), outB = (size_t)frames * b->S * esize(b->out_dtype);
+    SDRGPU_CHECK(b->pin_in.ensure(std::max<size_t>(inB, 1)));
+    SDRGPU_CHECK(b->pin_out.ensure(std::max<size_t>(outB, 1)));
+    SDRGPU_CHECK(b->dev_in.ensure(std::max<size_t>(inB, 1)));
+    SDRGPU_CHECK(b->dev_out.ensure(std::max<size_t>(outB, 1)));
+    if (frames > 0) std::memcpy(b->pin_in.p, in, inB);
+    if (frames > 0 && b->ragged()) std::memcpy(b->pin_out.p, out, outB);
+    SDRGPU_CHECK(b->order.follow(b->own));
+    OrderScope od(b->order, b->own);
+    if (frames > 0) SDRGPU_HIP(hipMemcpyAsync(b->dev_in.p, b->pin_in.p, inB, hipMemcpyHostToDevice, b->own));
+    if (frames > 0 && b->ragged()) SDRGPU_HIP(hipMemcpyAsync(b->dev_out.p, b->pin_out.p, outB, hipMemcpyHostToDevice, b->own));
+    const int rows = b->run(b->dev_in.p, frames, b->dev_out.p, b->own);
+    if (rows < 0) return rows;
+    b->lastRows = rows;
+    const size_t gotB = (size_t)rows * b->S * esize(b->out_dtype);
+    if (rows > 0) SDRGPU_HIP(hipMemcpyAsync(b->pin_out.p, b->dev_out.p, gotB, hipMemcpyDeviceToHost, b->own));
+    SDRGPU_HIP(hipStreamSynchronize(b->own));
+    if (rows > 0) std::memcpy(out, b->pin_out.p, gotB);
+    return rows;
+}
+
+extern "C" int sdrgpu_bank_out_counts(sdrgpu_bank* h, int* counts) {
+    NEED_BANK(h);
+    if (!counts) { set_error("bank_out_counts: null pointer"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(h->impl->device);
+    SDRGPU_HIP(hipDeviceSynchronize());
+    h->impl->counts(counts);
+    return SDRGPU_OK;
+}
+
+extern "C" int sdrgpu_bank_reset(sdrgpu_bank* h) {
+    NEED_BANK(h);
+    SDRGPU_SET_DEVICE(h->impl->device);
+    SDRGPU_HIP(hipDeviceSynchronize());   // (the state a queued call still reads is rewritten on the null stream)
+    SDRGPU_CHECK(h->impl->reset());
+    h->impl->lastRows = 0;
+    SDRGPU_HIP(hipDeviceSynchronize());
+    return SDRGPU_OK;
+}
+
+extern "C" int sdrgpu_bank_destroy(sdrgpu_bank* h) {
+    if (!h) return SDRGPU_OK;
+    if (h->impl) {
+        (void)hipSetDevice(h->impl->device);
+        (void)hipDeviceSynchronize();
+        delete h->impl;
+    }
+    delete h;
+    return SDRGPU_OK;
+}

@@ -41,13 +41,7 @@ __global__ void xlator_kernel(const float2* __restrict__ in, float2* __restrict_
 }
 
 // ----------------------------------------------------------- quadrature
-// demod/quadrature.h:41-56: arg(y * conj(d)) / dev (one expression for every kernel using it)
-__device__ __forceinline__ float quad_value(float2 y, float2 d, float invDev) {
-    const float br = d.x, bi = -d.y;
-    const float re = (y.x * br) - (y.y * bi);
-    const float im = (y.y * br) + (y.x * bi);
-    return quad_atan2f(im, re) * invDev;
-}
+// (quad_value: quad_value.h)
 __global__ void quad_kernel(const float2* __restrict__ in, float* __restrict__ out, int n, const float2* __restrict__ din,
                             float2* __restrict__ dinNext, float invDev) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

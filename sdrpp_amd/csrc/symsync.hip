@@ -14,23 +14,16 @@
 #include "sdrgpu_internal.h"
 #include "blocks.h"
 #include "symsync_kernels.h"
+#include "symsync_args.h"   // the argument checks, shared with bank.hip
 
 namespace sdrgpu {
-
-static bool finite_all(std::initializer_list<double> v) {
-    for (double x : v)
-        if (!std::isfinite(x)) return false;
-    return true;
-}
 
 struct FastAgcBlock : Block {
     FastAgcParams p{};
     float initGain = 1.0f;
     DevBuf state;
-    void set(double setPoint, double maxGain, double rate, double initGain_) {   // members are float (fast_agc.h:93-97)
-        p.setPoint = (float)setPoint;
-        p.maxGain = (float)maxGain;
-        p.rate = (float)rate;
+    void set(double setPoint, double maxGain, double rate, double initGain_) {
+        fast_agc_params(p, setPoint, maxGain, rate);
         initGain = (float)initGain_;
     }
     int setup(int dev, int dtype, double setPoint, double maxGain, double rate, double initGain_) {
@@ -73,19 +66,11 @@ struct FastAgcBlock : Block {
     }
 };
 
-// Frequencies and phases are rad/sample: a bound far above any meaningful value keeps the phase wrap
-// (a subtraction loop, phase_control_loop.h:82-85) to a few hundred steps per sample
-static constexpr double COSTAS_MAX_RAD = 1024.0;
-
 struct CostasBlock : Block {
     int order = 2;
     CostasParams p{};
     float initPhase = 0.0f, initFreq = 0.0f;
     DevBuf state;
-    static bool limits_ok(double minFreq, double maxFreq) {   // PhaseControlLoop: assert(maxFreq > minFreq)
-        return finite_all({minFreq, maxFreq}) && maxFreq > minFreq && std::fabs(minFreq) <= COSTAS_MAX_RAD &&
-               std::fabs(maxFreq) <= COSTAS_MAX_RAD;
-    }
     int setup(int dev, int order_, double bandwidth, double initPhase_, double initFreq_, double minFreq, double maxFreq) {
         device = dev;
         in_dtype = out_dtype = SDRGPU_C64;
@@ -130,21 +115,7 @@ struct MmBlock : Block {
     DevBuf state, hist, bank, soft;
     PinnedBuf countBuf;   // the call's output count, read back at the end of run()
     int lastCount = 0;
-    // Every output must consume at least one input sample: phase >= 0 before advance, freq >= minFreq and
-    // alpha * error >= -alpha, so floorf(phase) >= 1 when minFreq - alpha >= 1 (also in the floats the
-    // kernel computes with).
-    static bool params_ok(double omega, double omegaGain, double muGain, double rel) {
-        if (!finite_all({omega, omegaGain, muGain, rel}) || !(omega > 0.0) || !(rel > 0.0) || muGain < 0.0) return false;
-        if (omega * (1.0 - rel) - muGain < 1.0) return false;
-        return (float)(omega * (1.0 - rel)) - (float)muGain >= 1.0f && omega * (1.0 + rel) < 1e6;
-    }
-    void set_pcl() {   // pcl.init / setCoefficients / setFreqLimits arguments (mm.h:32, 48, 56, 70): doubles to float
-        p.pcl.alpha = (float)muGain;
-        p.pcl.beta = (float)omegaGain;
-        p.pcl.minFreq = (float)(omega * (1.0 - rel));
-        p.pcl.maxFreq = (float)(omega * (1.0 + rel));
-        p.omega = (float)omega;
-    }
+    void set_pcl() { mm_pcl_params(p, omega, omegaGain, muGain, rel); }
     int setup(int dev, int dtype, MmEpilogue e, int inStride, double omega_, double omegaGain_, double muGain_, double rel_,
               int P, int T) {
         device = dev;
@@ -168,7 +139,7 @@ struct MmBlock : Block {
         SDRGPU_HIP(hipMemset(hist.p, 0, hist.bytes));   // (the reference's work buffer starts uninitialised)
         return reset();
     }
-    // the capacity of a call: at most one output per input sample (params_ok)
+    // the capacity of a call: at most one output per input sample (mm_params_ok)
     int out_count(int count) override { return count; }
     int reset() override {   // mm.h:87-98: the state, not the history
         SDRGPU_SET_DEVICE(device);
@@ -258,10 +229,7 @@ static Block* make_fast_agc(int dev, int dtype, double setPoint, double maxGain,
 static Block* make_costas(int dev, int order, double bandwidth, double initPhase, double initFreq, double minFreq,
                           double maxFreq, int* rc) {
     auto* c = new CostasBlock();
-    if (!(order == 2 || order == 4 || order == 8) || !finite_all({bandwidth, initPhase, initFreq}) ||
-        std::fabs(initPhase) > COSTAS_MAX_RAD || std::fabs(initFreq) > COSTAS_MAX_RAD || !CostasBlock::limits_ok(minFreq, maxFreq)) {
-        set_error("costas: order %d not 2 / 4 / 8, or a phase / frequency not finite, beyond %g rad, or minFreq >= maxFreq", order,
-                  COSTAS_MAX_RAD);
+    if (!costas_args_ok(order, bandwidth, initPhase, initFreq, minFreq, maxFreq)) {
         *rc = SDRGPU_EARG;
         return c;
     }
@@ -271,11 +239,7 @@ static Block* make_costas(int dev, int order, double bandwidth, double initPhase
 static Block* make_mm(int dev, int dtype, MmEpilogue e, int inStride, double omega, double omegaGain, double muGain, double rel,
                       int P, int T, int* rc) {
     auto* m = new MmBlock();
-    if (P < 1 || P > SDRGPU_MM_MAX_PHASES || T < 1 || T > SDRGPU_MM_MAX_TAPS) {
-        set_error("mm: interpolator bank %d x %d outside [1, %d] x [1, %d]", P, T, SDRGPU_MM_MAX_PHASES, SDRGPU_MM_MAX_TAPS);
-        *rc = SDRGPU_EARG;
-    } else if (!MmBlock::params_ok(omega, omegaGain, muGain, rel)) {
-        set_error("mm: omega * (1 - omegaRelLimit) - muGain must be >= 1 (an output per input sample at most)");
+    if (!mm_args_ok(omega, omegaGain, muGain, rel, P, T)) {
         *rc = SDRGPU_EARG;
     } else {
         *rc = m->setup(dev, dtype, e, inStride, omega, omegaGain, muGain, rel, P, T);
@@ -304,8 +268,6 @@ static MmBlock* mm_of(sdrgpu_block* h) { return as_block<MmBlock>(h, "an MM bloc
 using namespace sdrgpu;
 
 // ------------------------------------------------------------------- C ABI
-static bool real_or_complex(int dtype) { return dtype == SDRGPU_F32 || dtype == SDRGPU_C64; }
-
 extern "C" int sdrgpu_fast_agc_create(sdrgpu_block** h, int device, int dtype, double setPoint, double maxGain, double rate,
                                       double initGain) {
     if (!h || !real_or_complex(dtype)) { set_error("fast_agc_create: bad argument"); return SDRGPU_EARG; }
@@ -347,7 +309,7 @@ extern "C" int sdrgpu_costas_set_bandwidth(sdrgpu_block* h, double bandwidth) {
 extern "C" int sdrgpu_costas_set_freq_limits(sdrgpu_block* h, double minFreq, double maxFreq) {
     auto* c = as_block<CostasBlock>(h, "a Costas loop");
     if (!c) return SDRGPU_EARG;
-    if (!CostasBlock::limits_ok(minFreq, maxFreq)) { set_error("costas: bad frequency limits"); return SDRGPU_EARG; }
+    if (!costas_limits_ok(minFreq, maxFreq)) { set_error("costas: bad frequency limits"); return SDRGPU_EARG; }
     c->p.pcl.minFreq = (float)minFreq;
     c->p.pcl.maxFreq = (float)maxFreq;
     c->p.clampNow = 1;
@@ -365,7 +327,7 @@ extern "C" int sdrgpu_mm_create(sdrgpu_block** h, int device, int dtype, double 
 static int mm_set(sdrgpu_block* h, double omega, double omegaGain, double muGain, double rel, bool newOmega) {
     MmBlock* m = mm_of(h);
     if (!m) return SDRGPU_EARG;
-    if (!MmBlock::params_ok(omega, omegaGain, muGain, rel)) {
+    if (!mm_params_ok(omega, omegaGain, muGain, rel)) {
         set_error("mm: omega * (1 - omegaRelLimit) - muGain must be >= 1 (an output per input sample at most)");
         return SDRGPU_EARG;
     }

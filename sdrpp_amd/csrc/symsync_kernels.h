@@ -12,7 +12,9 @@
 // The three loops are data-dependent recurrences: one workgroup of LOOP_NT lanes per stream walks the
 // call in LOOP_CHUNK-sample chunks staged in LDS, lane 0 runs the recurrence in the reference's
 // operation order, all lanes store the results (serial_chunks.h). State lives on the device between
-// calls and is written back by lane 0. Nothing here uses atomics.
+// calls and is written back by lane 0. Nothing here uses atomics. The per-sample step of each loop is a
+// __forceinline__ function (fast_agc_step, costas_step, mm_step) that the lane-per-stream kernels of
+// bank_kernels.h call too: a recurrence is stated once.
 #pragma once
 #include "serial_chunks.h"
 
@@ -41,6 +43,15 @@ struct FastAgcParams {
     float setGain;   // FastAGC::setGain latched at this call ...
     int hasGain;     // ... when non-zero
 };
+// one sample (fast_agc.h:66-76): the scaled sample out, the gain moved on
+template <typename DT>
+__device__ __forceinline__ DT fast_agc_step(const FastAgcParams& p, DT x, float& gain) {
+    const DT o = scale_of(x, gain);
+    const float amp = amp_of(o);
+    gain += (p.setPoint - amp) * p.rate;
+    if (gain > p.maxGain) gain = p.maxGain;
+    return o;
+}
 template <typename DT>
 __global__ __launch_bounds__(LOOP_NT) void fast_agc_kernel(const DT* __restrict__ in, DT* __restrict__ out, int count,
                                                            FastAgcParams p, float* __restrict__ st) {
@@ -48,13 +59,7 @@ __global__ __launch_bounds__(LOOP_NT) void fast_agc_kernel(const DT* __restrict_
     float gain = p.hasGain ? p.setGain : *st;
     serial_chunks(
         count, [&](int i0, int i) { X[i] = in[i0 + i]; },
-        [&](int i) {
-            const DT o = scale_of(X[i], gain);
-            X[i] = o;
-            const float amp = amp_of(o);
-            gain += (p.setPoint - amp) * p.rate;
-            if (gain > p.maxGain) gain = p.maxGain;
-        },
+        [&](int i) { X[i] = fast_agc_step(p, X[i], gain); },
         [&](int i0, int i) { out[i0 + i] = X[i]; });
     if (threadIdx.x == 0) *st = gain;
 }
@@ -78,6 +83,19 @@ __device__ __forceinline__ float costas_error(float re, float im) {   // costas.
     }
     return (err < -1.0f) ? -1.0f : ((1.0f < err) ? 1.0f : err);   // std::clamp<float>
 }
+// one sample (costas.h:17-24, phase_control_loop.h:58-85): the derotated sample out, the loop moved on
+template <int ORDER>
+__device__ __forceinline__ float2 costas_step(const PclParams& p, float2 v, float& phase, float& freq) {
+    const float PI = 3.1415926535f;                            // FL_M_PI (math/constants.h:4)
+    const float minPhase = -PI, maxPhase = PI, phaseDelta = maxPhase - minPhase;
+    const float vr = cosf(-phase), vi = sinf(-phase);           // math::phasor(-pcl.phase)
+    const float re = (v.x * vr) - (v.y * vi);                   // complex_t::operator* (types.h:23)
+    const float im = (v.y * vr) + (v.x * vi);
+    pcl_advance(p, costas_error<ORDER>(re, im), phase, freq);
+    while (phase > maxPhase) phase -= phaseDelta;               // clampPhase (:82-85)
+    while (phase < minPhase) phase += phaseDelta;
+    return make_float2(re, im);
+}
 // state: (phase, freq)
 template <int ORDER>
 __global__ __launch_bounds__(LOOP_NT) void costas_kernel(const float2* __restrict__ in, float2* __restrict__ out, int count,
@@ -85,20 +103,9 @@ __global__ __launch_bounds__(LOOP_NT) void costas_kernel(const float2* __restric
     __shared__ float2 X[LOOP_CHUNK];
     float phase = st->x, freq = st->y;
     if (p.clampNow) pcl_clamp_freq(p.pcl, freq);
-    const float PI = 3.1415926535f;                            // FL_M_PI (math/constants.h:4)
-    const float minPhase = -PI, maxPhase = PI, phaseDelta = maxPhase - minPhase;
     serial_chunks(
         count, [&](int i0, int i) { X[i] = in[i0 + i]; },
-        [&](int i) {
-            const float2 v = X[i];
-            const float vr = cosf(-phase), vi = sinf(-phase);   // math::phasor(-pcl.phase)
-            const float re = (v.x * vr) - (v.y * vi);           // complex_t::operator* (types.h:23)
-            const float im = (v.y * vr) + (v.x * vi);
-            X[i] = make_float2(re, im);
-            pcl_advance(p.pcl, costas_error<ORDER>(re, im), phase, freq);
-            while (phase > maxPhase) phase -= phaseDelta;       // clampPhase (:82-85)
-            while (phase < minPhase) phase += phaseDelta;
-        },
+        [&](int i) { X[i] = costas_step<ORDER>(p.pcl, X[i], phase, freq); },
         [&](int i0, int i) { out[i0 + i] = X[i]; });
     if (threadIdx.x == 0) *st = make_float2(phase, freq);
 }
@@ -133,6 +140,49 @@ template <typename DT>
 __device__ __forceinline__ DT mm_load(const DT* in, size_t i, int stride) {
     if constexpr (sizeof(DT) == 4) return in[i * stride];
     else return in[i];
+}
+
+// One output (mm.h:109-147) at the loop state s: the interpolated symbol out; the error, the loop and the
+// offset moved on. x(k): sample k of the work buffer from s.offset; b(ph, k): tap k of interpolator phase ph.
+template <typename DT, typename XF, typename BF>
+__device__ __forceinline__ DT mm_step(const MmParams& p, MmState& s, XF x, BF b) {
+    // mm.h:111: clamp<int>(floorf(phase * P), 0, P - 1)
+    int ph = (int)floorf(s.phase * (float)p.P);
+    ph = ph < 0 ? 0 : (ph > p.P - 1 ? p.P - 1 : ph);
+    DT o;
+    float error;
+    if constexpr (sizeof(DT) == 4) {
+        float acc = 0.0f;                    // volk_32f_x2_dot_prod_32f_generic
+        for (int k = 0; k < p.T; k++) acc += x(k) * b(ph, k);
+        o = acc;
+        error = (step_of(s.lastOut) * acc) - (s.lastOut * step_of(acc));   // :122-123
+        s.lastOut = acc;
+    } else {
+        float ar = 0.0f, ai = 0.0f;          // volk_32fc_32f_dot_prod_32fc_generic
+        for (int k = 0; k < p.T; k++) {
+            const DT v = x(k);
+            const float t = b(ph, k);
+            ar += v.x * t;
+            ai += v.y * t;
+        }
+        o = make_float2(ar, ai);
+        s.p2 = s.p1; s.p1 = s.p0; s.c2 = s.c1; s.c1 = s.c0;            // :127-134
+        s.p0 = make_float2(ar, ai);
+        s.c0 = make_float2(step_of(ar), step_of(ai));
+        // :137 (((p0 - p2) * c1.conj()) - ((c0 - c2) * p1.conj())).re
+        const float dr = s.p0.x - s.p2.x, di = s.p0.y - s.p2.y;
+        const float er = s.c0.x - s.c2.x, ei = s.c0.y - s.c2.y;
+        const float a = (dr * s.c1.x) - (di * (-s.c1.y));
+        const float c = (er * s.p1.x) - (ei * (-s.p1.y));
+        error = a - c;
+    }
+    if (error > 1.0f) error = 1.0f;          // :141-142
+    if (error < -1.0f) error = -1.0f;
+    pcl_advance(p.pcl, error, s.phase, s.freq);
+    const float delta = floorf(s.phase);
+    s.offset = (int)((float)s.offset + delta);   // int += float
+    s.phase -= delta;
+    return o;
 }
 
 // One workgroup. The work buffer of mm.h:102 is [hist (T - 1 samples) || in (count samples)]; chunk c
@@ -173,41 +223,8 @@ __global__ __launch_bounds__(LOOP_NT) void mm_kernel(const DT* __restrict__ in, 
         if (t == 0) {
             int no = 0;
             while (s.offset >= i0 && s.offset < i0 + n && no < n) {
-                // mm.h:111: clamp<int>(floorf(phase * P), 0, P - 1)
-                int ph = (int)floorf(s.phase * (float)p.P);
-                ph = ph < 0 ? 0 : (ph > p.P - 1 ? p.P - 1 : ph);
                 const DT* x = &W[s.offset - i0];
-                const float* b = &B[ph * T];
-                float error;
-                if constexpr (sizeof(DT) == 4) {
-                    float acc = 0.0f;                    // volk_32f_x2_dot_prod_32f_generic
-                    for (int k = 0; k < T; k++) acc += x[k] * b[k];
-                    O[no++] = acc;
-                    error = (step_of(s.lastOut) * acc) - (s.lastOut * step_of(acc));   // :122-123
-                    s.lastOut = acc;
-                } else {
-                    float ar = 0.0f, ai = 0.0f;          // volk_32fc_32f_dot_prod_32fc_generic
-                    for (int k = 0; k < T; k++) {
-                        ar += x[k].x * b[k];
-                        ai += x[k].y * b[k];
-                    }
-                    O[no++] = make_float2(ar, ai);
-                    s.p2 = s.p1; s.p1 = s.p0; s.c2 = s.c1; s.c1 = s.c0;            // :127-134
-                    s.p0 = make_float2(ar, ai);
-                    s.c0 = make_float2(step_of(ar), step_of(ai));
-                    // :137 (((p0 - p2) * c1.conj()) - ((c0 - c2) * p1.conj())).re
-                    const float dr = s.p0.x - s.p2.x, di = s.p0.y - s.p2.y;
-                    const float er = s.c0.x - s.c2.x, ei = s.c0.y - s.c2.y;
-                    const float a = (dr * s.c1.x) - (di * (-s.c1.y));
-                    const float c = (er * s.p1.x) - (ei * (-s.p1.y));
-                    error = a - c;
-                }
-                if (error > 1.0f) error = 1.0f;          // :141-142
-                if (error < -1.0f) error = -1.0f;
-                pcl_advance(p.pcl, error, s.phase, s.freq);
-                const float delta = floorf(s.phase);
-                s.offset = (int)((float)s.offset + delta);   // int += float
-                s.phase -= delta;
+                O[no++] = mm_step<DT>(p, s, [&](int k) { return x[k]; }, [&](int ph, int k) { return B[ph * T + k]; });
             }
             nOut = no;
         }
@@ -248,12 +265,13 @@ __global__ __launch_bounds__(LOOP_NT) void mm_kernel(const DT* __restrict__ in, 
 }
 
 // --------------------------------------------------- slicer, differential decoder
-__global__ void slicer_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int n) {
+// (static: bank_kernels.h includes this header from a second translation unit)
+static __global__ void slicer_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = in[i] > 0.0f;
 }
 // last[0]: the symbol before in[0]; last[1] <- in[n - 1] (the host swaps the two per call)
-__global__ void diff_decode_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int n, int modulus,
+static __global__ void diff_decode_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int n, int modulus,
                                    const int* __restrict__ last, int* __restrict__ next) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

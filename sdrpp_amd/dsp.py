@@ -615,6 +615,131 @@ class RDSBits(Block):
         return out
 
 
+# ---- stream banks (include/sdrgpu.h "stream banks") --------------------------
+class Bank:
+    """Owns one sdrgpu_bank handle: S independent streams with shared parameters, element m of stream
+    k at x[m, k] (the channelizer's layout). ``process(x)`` takes (frames, S) and returns (rows, S);
+    after a call of a bank that ends in MM, ``counts`` is the int32[S] array of per-stream output
+    counts, rows is the largest of them, and the elements of a row past a stream's count keep what
+    ``out`` held (zeros where ``process`` allocates it)."""
+
+    def __init__(self, handle, in_dtype, out_dtype):
+        self._h = handle
+        self.in_dtype = in_dtype
+        self.out_dtype = out_dtype
+        self.streams = check(lib.sdrgpu_bank_streams(self._h))
+
+    def out_rows(self, frames):
+        return check(lib.sdrgpu_bank_out_rows(self._h, int(frames)))
+
+    def process(self, x, out=None):
+        x = np.ascontiguousarray(x, dtype=self.in_dtype)
+        if x.ndim != 2 or x.shape[1] != self.streams:
+            raise ValueError(f"a bank of {self.streams} streams takes (frames, {self.streams}), not {x.shape}")
+        frames = x.shape[0]
+        cap = max(self.out_rows(frames), 1)
+        if out is None:
+            out = np.zeros((cap, self.streams), self.out_dtype)
+        elif out.dtype != self.out_dtype or out.shape != (cap, self.streams) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a contiguous {np.dtype(self.out_dtype)} array of shape {(cap, self.streams)}")
+        rows = check(lib.sdrgpu_bank_process(self._h, _fptr(x), frames, _fptr(out)))
+        return out[:rows]
+
+    def process_dev(self, in_ptr, frames, out_ptr, stream=None):
+        return check(lib.sdrgpu_bank_process_dev(self._h, _vp(in_ptr), int(frames), _vp(out_ptr), _vp(stream or 0)))
+
+    @property
+    def counts(self):
+        c = np.empty(self.streams, np.int32)
+        check(lib.sdrgpu_bank_out_counts(self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return c
+
+    def reset(self):
+        check(lib.sdrgpu_bank_reset(self._h))
+
+    def close(self):
+        if self._h:
+            lib.sdrgpu_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BankQuadrature(Bank):
+    """dsp::demod::Quadrature per stream; deviation in rad/sample."""
+
+    def __init__(self, streams, deviation_rad, device=0):
+        super().__init__(_make(lib.sdrgpu_bank_quadrature_create, device, int(streams), float(deviation_rad)), np.complex64,
+                         np.float32)
+
+
+class BankFIR(Bank):
+    """dsp::filter::FIR<D, float> per stream: real taps shared by all streams."""
+
+    def __init__(self, streams, taps, complex_data=True, device=0):
+        t = np.ascontiguousarray(taps, np.float32)
+        self._taps = t
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_bank_fir_create, device, int(streams), C64 if complex_data else F32, _fptr(t), int(t.shape[0]))
+        super().__init__(h, npd, npd)
+
+
+class BankFastAGC(Bank):
+    """dsp::loop::FastAGC<T> per stream."""
+
+    def __init__(self, streams, set_point, max_gain, rate, init_gain=1.0, complex_data=False, device=0):
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_bank_fast_agc_create, device, int(streams), C64 if complex_data else F32, float(set_point),
+                  float(max_gain), float(rate), float(init_gain))
+        super().__init__(h, npd, npd)
+
+
+class BankCostas(Bank):
+    """dsp::loop::Costas<ORDER> per stream; arguments as Costas."""
+
+    def __init__(self, streams, order, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-float(np.float32(3.1415926535)),
+                 max_freq=float(np.float32(3.1415926535)), device=0):
+        h = _make(lib.sdrgpu_bank_costas_create, device, int(streams), int(order), float(bandwidth), float(init_phase),
+                  float(init_freq), float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankMM(Bank):
+    """dsp::clock_recovery::MM<T> per stream; arguments as MM. ``out_rows`` is the capacity (= frames)."""
+
+    def __init__(self, streams, omega, omega_gain, mu_gain, omega_rel_limit, interp_phases=128, interp_taps=8, complex_data=False,
+                 device=0):
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_bank_mm_create, device, int(streams), C64 if complex_data else F32, float(omega), float(omega_gain),
+                  float(mu_gain), float(omega_rel_limit), int(interp_phases), int(interp_taps))
+        super().__init__(h, npd, npd)
+
+
+class BankPSK(Bank):
+    """dsp::demod::PSK<ORDER> per stream: complex64 samples -> complex64 symbols; arguments as PSK."""
+
+    def __init__(self, streams, order, symbolrate, samplerate, rrc_taps, rrc_beta, agc_rate, costas_bandwidth, omega_gain, mu_gain,
+                 omega_rel_limit=0.01, device=0):
+        h = _make(lib.sdrgpu_bank_psk_create, device, int(streams), int(order), float(symbolrate), float(samplerate), int(rrc_taps),
+                  float(rrc_beta), float(agc_rate), float(costas_bandwidth), float(omega_gain), float(mu_gain),
+                  float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankGFSK(Bank):
+    """dsp::demod::GFSK per stream: complex64 samples -> float32 soft symbols; arguments as GFSK."""
+
+    def __init__(self, streams, symbolrate, samplerate, deviation, rrc_taps, rrc_beta, omega_gain, mu_gain, omega_rel_limit=0.01,
+                 device=0):
+        h = _make(lib.sdrgpu_bank_gfsk_create, device, int(streams), float(symbolrate), float(samplerate), float(deviation),
+                  int(rrc_taps), float(rrc_beta), float(omega_gain), float(mu_gain), float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.float32)
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
