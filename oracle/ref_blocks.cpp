@@ -1,0 +1,323 @@
+// Second reference probe (test infrastructure; built only where the reference tree exists, output in
+// oracle/_ref/). Includes the reference's OWN stateful block headers -- loops, symbol recovery, IF
+// noise reduction and the PSK / GFSK chains -- from where the reference lies and calls their
+// process() directly, so the numpy restatements in tests/_restated.py, the C oracle's loops and the
+// device kernels are pinned against reference code, not against a reading of it. VOLK, FFTW and the
+// host runtime are replaced by oracle/ref_standins.cpp. No thread is ever started.
+//
+//   ref_blocks <mode> <calls> [parameters...]
+//
+// <calls> is a comma list run in order: a number is one process() call of that many input samples
+// (0 included); for the MM modes `r` calls reset(), `o<omega>` setOmega() and `i<P>x<T>`
+// setInterpParams(). Input samples are raw on stdin (as many as the calls sum to). stdout: int32
+// number of process() calls, int32 output count of each, then every call's outputs, raw, in order.
+// The rds mode appends every call's bits (uint8) after the soft symbols.
+//
+//   fastagc_f|fastagc_c  setPoint maxGain rate initGain     loop::FastAGC<float|complex_t>
+//   costas  order bandwidth [initPhase initFreq minFreq maxFreq]
+//                                                           loop::Costas<2|4|8>, init() as wfm.h calls it
+//   mm_f|mm_c  omega omegaGain muGain omegaRelLimit         clock_recovery::MM<float|complex_t> (128, 8)
+//   slicer                                                  digital::BinarySlicer
+//   diff  modulus initSym                                   digital::DifferentialDecoder
+//   nb  rate level                                          noise_reduction::NoiseBlanker
+//   squelch  level                                          noise_reduction::Squelch, one object
+//   fmif  bins                                              noise_reduction::FMIF
+//   agc_f|agc_c  setPoint attack decay maxGain maxOutputAmp initGain   loop::AGC<float|complex_t>
+//   dcb_f|dcb_c  rate                                       correction::DCBlocker<float|complex_t>
+//   deemp_f|deemp_s  tau samplerate                         filter::Deemphasis<float|stereo_t>
+//   psk  order symbolrate samplerate rrcTaps rrcBeta agcRate costasBw omegaGain muGain omegaRelLimit
+//   gfsk  symbolrate samplerate deviation rrcTaps rrcBeta omegaGain muGain omegaRelLimit
+//   rds                                                     the blocks and calls of the radio module's wfm.h:57-68
+// Design code (no stdin, <calls> ignored; stdout float32 only):
+//   rrc  count beta Ts                                      taps::rootRaisedCosine<float>
+//   mmbank  P T                                             the bank MM builds for itself, [P][T]
+//   fmifwin  bins                                           the window FMIF builds for itself
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <new>
+#include <string>
+#include <vector>
+#include <dsp/types.h>
+#include <dsp/loop/fast_agc.h>
+#include <dsp/loop/costas.h>
+#include <dsp/loop/agc.h>
+#include <dsp/clock_recovery/mm.h>
+#include <dsp/digital/binary_slicer.h>
+#include <dsp/digital/differential_decoder.h>
+#include <dsp/noise_reduction/noise_blanker.h>
+#include <dsp/noise_reduction/squelch.h>
+#include <dsp/noise_reduction/fm_if.h>
+#include <dsp/correction/dc_blocker.h>
+#include <dsp/filter/deephasis.h>
+#include <dsp/filter/fir.h>
+#include <dsp/taps/root_raised_cosine.h>
+#include <dsp/taps/band_pass.h>
+#include <dsp/convert/complex_to_real.h>
+#include <dsp/math/hz_to_rads.h>
+#include <dsp/demod/psk.h>
+#include <dsp/demod/gfsk.h>
+
+using dsp::complex_t;
+using dsp::stereo_t;
+
+struct Op {
+    char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams
+    int count = 0, a = 0, b = 0;
+    double v = 0.0;
+};
+
+static std::vector<Op> parseCalls(const char* s) {
+    std::vector<Op> ops;
+    std::string str(s), tok;
+    size_t pos = 0;
+    while (pos <= str.size()) {
+        size_t e = str.find(',', pos);
+        if (e == std::string::npos) { e = str.size(); }
+        tok = str.substr(pos, e - pos);
+        pos = e + 1;
+        if (tok.empty()) { continue; }
+        Op op;
+        if (tok[0] == 'r') { op.kind = 'r'; }
+        else if (tok[0] == 'o') { op.kind = 'o'; op.v = strtod(tok.c_str() + 1, NULL); }
+        else if (tok[0] == 'i') { op.kind = 'i'; sscanf(tok.c_str() + 1, "%dx%d", &op.a, &op.b); }
+        else { op.kind = 'p'; op.count = atoi(tok.c_str()); }
+        ops.push_back(op);
+    }
+    return ops;
+}
+
+template <class T>
+static std::vector<T> readInput(size_t n) {
+    std::vector<T> x(n + 1);
+    if (fread(x.data(), sizeof(T), n, stdin) != n) { fprintf(stderr, "ref_blocks: short input\n"); exit(3); }
+    return x;
+}
+
+// Runs the process() calls of `ops` over stdin; `other` handles the remaining kinds.
+template <class I, class O>
+static int runCalls(const std::vector<Op>& ops, std::function<int(int, I*, O*)> proc,
+                    std::function<void(const Op&)> other = nullptr,
+                    std::vector<uint8_t>* second = nullptr, std::function<void(int, uint8_t*)> fillSecond = nullptr) {
+    size_t total = 0;
+    for (auto& op : ops) { total += op.kind == 'p' ? op.count : 0; }
+    std::vector<I> x = readInput<I>(total);
+    std::vector<O> y(total + 1);
+    std::vector<int32_t> counts;
+    size_t ip = 0, op_ = 0;
+    for (auto& op : ops) {
+        if (op.kind != 'p') {
+            if (!other) { fprintf(stderr, "ref_blocks: this mode takes process() calls only\n"); return 2; }
+            other(op);
+            continue;
+        }
+        int n = proc(op.count, x.data() + ip, y.data() + op_);
+        if (second) {
+            size_t at = second->size();
+            second->resize(at + n);
+            fillSecond(n, second->data() + at);
+        }
+        counts.push_back(n);
+        ip += op.count;
+        op_ += n;
+    }
+    int32_t nc = (int32_t)counts.size();
+    fwrite(&nc, sizeof(nc), 1, stdout);
+    fwrite(counts.data(), sizeof(int32_t), counts.size(), stdout);
+    fwrite(y.data(), sizeof(O), op_, stdout);
+    if (second) { fwrite(second->data(), 1, second->size(), stdout); }
+    return 0;
+}
+
+// A block in zero-filled storage, as an object of static storage duration would be: some members have
+// no initialiser and are not set by init() (Quadrature's previous sample, demod/quadrature.h:84), so a
+// block on the stack would start from whatever the stack held. Never destroyed: the process ends.
+template <class T>
+static T& zeroed() {
+    return *new (calloc(1, sizeof(T))) T();
+}
+
+template <class T>
+struct OpenMM : dsp::clock_recovery::MM<T> {
+    dsp::multirate::PolyphaseBank<float>& bank() { return this->interpBank; }
+};
+
+struct OpenFMIF : dsp::noise_reduction::FMIF {
+    float* win() { return fftWin; }
+};
+
+template <class T>
+static int runFastAGC(const std::vector<Op>& ops, char** p) {
+    dsp::loop::FastAGC<T>& b = zeroed<dsp::loop::FastAGC<T>>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]));
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); });
+}
+
+template <int ORDER>
+static int runCostas(const std::vector<Op>& ops, int np, char** p) {
+    dsp::loop::Costas<ORDER>& b = zeroed<dsp::loop::Costas<ORDER>>();
+    if (np == 1) { b.init(NULL, atof(p[0])); }
+    else { b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]), atof(p[4])); }
+    return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); });
+}
+
+template <class T>
+static int runMM(const std::vector<Op>& ops, char** p) {
+    dsp::clock_recovery::MM<T>& b = zeroed<dsp::clock_recovery::MM<T>>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]));
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); }, [&](const Op& op) {
+        if (op.kind == 'r') { b.reset(); }
+        if (op.kind == 'o') { b.setOmega(op.v); }
+        if (op.kind == 'i') { b.setInterpParams(op.a, op.b); }
+    });
+}
+
+template <class T>
+static int runAGC(const std::vector<Op>& ops, char** p) {
+    dsp::loop::AGC<T>& b = zeroed<dsp::loop::AGC<T>>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]), atof(p[4]), atof(p[5]));
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); });
+}
+
+template <class T>
+static int runDCB(const std::vector<Op>& ops, char** p) {
+    dsp::correction::DCBlocker<T>& b = zeroed<dsp::correction::DCBlocker<T>>();
+    b.init(NULL, atof(p[0]));
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); });
+}
+
+template <class T>
+static int runDeemp(const std::vector<Op>& ops, char** p) {
+    dsp::filter::Deemphasis<T>& b = zeroed<dsp::filter::Deemphasis<T>>();
+    b.init(NULL, atof(p[0]), atof(p[1]));
+    // (an empty call is not passed on: filter/deephasis.h:58-72 writes out[0] and reads out[count - 1])
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return n ? b.process(n, in, out) : 0; });
+}
+
+template <int ORDER>
+static int runPSK(const std::vector<Op>& ops, char** p) {
+    dsp::demod::PSK<ORDER>& b = zeroed<dsp::demod::PSK<ORDER>>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atoi(p[2]), atof(p[3]), atof(p[4]), atof(p[5]), atof(p[6]), atof(p[7]), atof(p[8]));
+    return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); });
+}
+
+static int runRDS(const std::vector<Op>& ops) {
+    // the members and init calls of the radio module's WFM demodulator; the stream pointers are
+    // NULL because process() is called directly, block by block, in the order the streams connect
+    dsp::loop::FastAGC<complex_t>& agc = zeroed<dsp::loop::FastAGC<complex_t>>();
+    dsp::loop::Costas<2>& costas = zeroed<dsp::loop::Costas<2>>();
+    dsp::loop::Costas<2>& costas2 = zeroed<dsp::loop::Costas<2>>();
+    dsp::tap<complex_t> taps;
+    dsp::filter::FIR<complex_t, complex_t>& fir = zeroed<dsp::filter::FIR<complex_t, complex_t>>();
+    dsp::clock_recovery::MM<float>& recov = zeroed<dsp::clock_recovery::MM<float>>();
+    dsp::digital::DifferentialDecoder& diff = zeroed<dsp::digital::DifferentialDecoder>();
+    agc.init(NULL, 1.0, 1e6, 0.1);
+    costas.init(NULL, 0.005f);
+    taps = dsp::taps::bandPass<complex_t>(0, 2375, 100, 5000);
+    fir.init(NULL, taps);
+    double baudfreq = dsp::math::hzToRads(2375.0 / 2.0, 5000);
+    costas2.init(NULL, 0.01, 0.0, baudfreq, baudfreq - (baudfreq * 0.1), baudfreq + (baudfreq * 0.1));
+    recov.init(NULL, 5000.0 / (2375.0 / 2.0), 1e-6, 0.01, 0.01);
+    diff.init(NULL, 2);
+    size_t cap = 1;
+    for (auto& op : ops) { cap = std::max<size_t>(cap, op.count + 1); }
+    std::vector<complex_t> a(cap), b(cap);
+    std::vector<float> f(cap);
+    std::vector<uint8_t> s(cap), bits;
+    float* soft = NULL;
+    return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) {
+        agc.process(n, in, a.data());
+        costas.process(n, a.data(), b.data());
+        fir.process(n, b.data(), a.data());
+        costas2.process(n, a.data(), b.data());
+        dsp::convert::ComplexToReal::process(n, b.data(), f.data());
+        soft = out;
+        return recov.process(n, f.data(), out);
+    }, nullptr, &bits, [&](int m, uint8_t* out) {
+        dsp::digital::BinarySlicer::process(m, soft, s.data());
+        diff.process(m, s.data(), out);
+    });
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) { return 2; }
+    std::string mode = argv[1];
+    std::vector<Op> ops = parseCalls(argv[2]);
+    char** p = argv + 3;
+    int np = argc - 3;
+
+    if (mode == "fastagc_f" && np == 4) { return runFastAGC<float>(ops, p); }
+    if (mode == "fastagc_c" && np == 4) { return runFastAGC<complex_t>(ops, p); }
+    if (mode == "costas" && (np == 2 || np == 6)) {
+        int order = atoi(p[0]);
+        if (order == 2) { return runCostas<2>(ops, np - 1, p + 1); }
+        if (order == 4) { return runCostas<4>(ops, np - 1, p + 1); }
+        if (order == 8) { return runCostas<8>(ops, np - 1, p + 1); }
+        return 2;
+    }
+    if (mode == "mm_f" && np == 4) { return runMM<float>(ops, p); }
+    if (mode == "mm_c" && np == 4) { return runMM<complex_t>(ops, p); }
+    if (mode == "slicer" && np == 0) {
+        return runCalls<float, uint8_t>(ops, [&](int n, float* in, uint8_t* out) { return dsp::digital::BinarySlicer::process(n, in, out); });
+    }
+    if (mode == "diff" && np == 2) {
+        dsp::digital::DifferentialDecoder& b = zeroed<dsp::digital::DifferentialDecoder>();
+        b.init(NULL, atoi(p[0]), atoi(p[1]));
+        return runCalls<uint8_t, uint8_t>(ops, [&](int n, uint8_t* in, uint8_t* out) { return b.process(n, in, out); });
+    }
+    if (mode == "nb" && np == 2) {
+        dsp::noise_reduction::NoiseBlanker& b = zeroed<dsp::noise_reduction::NoiseBlanker>();
+        b.init(NULL, atof(p[0]), atof(p[1]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); });
+    }
+    if (mode == "squelch" && np == 1) {
+        dsp::noise_reduction::Squelch& b = zeroed<dsp::noise_reduction::Squelch>();
+        b.init(NULL, atof(p[0]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); });
+    }
+    if (mode == "fmif" && np == 1) {
+        dsp::noise_reduction::FMIF& b = zeroed<dsp::noise_reduction::FMIF>();
+        b.init(NULL, atoi(p[0]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); });
+    }
+    if (mode == "agc_f" && np == 6) { return runAGC<float>(ops, p); }
+    if (mode == "agc_c" && np == 6) { return runAGC<complex_t>(ops, p); }
+    if (mode == "dcb_f" && np == 1) { return runDCB<float>(ops, p); }
+    if (mode == "dcb_c" && np == 1) { return runDCB<complex_t>(ops, p); }
+    if (mode == "deemp_f" && np == 2) { return runDeemp<float>(ops, p); }
+    if (mode == "deemp_s" && np == 2) { return runDeemp<stereo_t>(ops, p); }
+    if (mode == "psk" && np == 10) {
+        int order = atoi(p[0]);
+        if (order == 2) { return runPSK<2>(ops, p + 1); }
+        if (order == 4) { return runPSK<4>(ops, p + 1); }
+        return 2;
+    }
+    if (mode == "gfsk" && np == 8) {
+        dsp::demod::GFSK& b = zeroed<dsp::demod::GFSK>();
+        b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atoi(p[3]), atof(p[4]), atof(p[5]), atof(p[6]), atof(p[7]));
+        return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) { return b.process(n, in, out); });
+    }
+    if (mode == "rds" && np == 0) { return runRDS(ops); }
+
+    if (mode == "rrc" && np == 3) {
+        dsp::tap<float> t = dsp::taps::rootRaisedCosine<float>(atoi(p[0]), atof(p[1]), atof(p[2]));
+        fwrite(t.taps, sizeof(float), t.size, stdout);
+        return 0;
+    }
+    if (mode == "mmbank" && np == 2) {
+        OpenMM<float>& b = zeroed<OpenMM<float>>();
+        b.init(NULL, 4.0, 2.5e-5, 0.01, 0.01, atoi(p[0]), atoi(p[1]));
+        auto& bank = b.bank();
+        for (int i = 0; i < bank.phaseCount; i++) { fwrite(bank.phases[i], sizeof(float), bank.tapsPerPhase, stdout); }
+        return 0;
+    }
+    if (mode == "fmifwin" && np == 1) {
+        OpenFMIF& b = zeroed<OpenFMIF>();
+        b.init(NULL, atoi(p[0]));
+        fwrite(b.win(), sizeof(float), atoi(p[0]), stdout);
+        return 0;
+    }
+    fprintf(stderr, "ref_blocks: unknown mode or wrong parameter count\n");
+    return 2;
+}

@@ -7,12 +7,15 @@
  * cpu_baseline leg may load it.
  *
  * Every function cites the reference file:line it restates (paths relative to
- * the qrp73/SDRPP tree, core/src/...). Parity status: the reference hot path
- * cannot be compiled here (VOLK/FFTW/fmt absent) and ships no DSP
- * tests or golden vectors, so the arithmetic that lives in VOLK/FFTW is
- * restated from its published semantics and pinned by the known-answer
- * properties and committed fixtures described in DESIGN.md ("parity pinned by
- * known answers, reference binary unavailable").
+ * the qrp73/SDRPP tree, core/src/...). Parity status: VOLK, FFTW and fmt are
+ * absent here and the reference ships no DSP tests or golden vectors, so the
+ * arithmetic that lives in VOLK/FFTW is restated from its published semantics
+ * and pinned by the known-answer properties and committed fixtures described
+ * in DESIGN.md. The reference's own headers do compile over stand-ins for the
+ * few library calls they make: ref_probe.cpp (windows, taps, quadrature) and
+ * ref_blocks.cpp (the loops of this file among them: AGC, DC blocker,
+ * de-emphasis) record their outputs in tests/golden/ref_*.npz, which
+ * tests/test_ref_pinned.py and tests/test_ref_blocks.py hold this library to.
  *
  * Two accumulation modes for every dot product:
  *   precise=1  fp64 accumulation, rounded once to float (the parity truth)

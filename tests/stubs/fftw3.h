@@ -1,6 +1,7 @@
-// Declaration-only stand-in for FFTW3's single-precision API, used ONLY by
-// tests/test_overlay_syntax.py (`g++ -fsyntax-only` of the overlay inside the reference tree; FFTW is
-// not installed in this image). Published fftw3.h signatures; nothing is defined, linked or run.
+// Declaration-only stand-in for FFTW3's single-precision API (FFTW is not installed in this image).
+// Published fftw3.h signatures; nothing is defined here. Used by the overlay tests (`g++ -fsyntax-only`
+// of the overlay inside the reference tree) and by oracle/ref_blocks.cpp, whose fftwf_* definitions are
+// the fp64 direct DFT of oracle/ref_standins.cpp.
 #pragma once
 #include <cstddef>
 typedef float fftwf_complex[2];

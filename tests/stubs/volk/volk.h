@@ -1,9 +1,12 @@
-// Declaration-only stand-in for VOLK's public header, used ONLY by tests/test_overlay_syntax.py to
-// run `g++ -fsyntax-only` over the drop-in overlay placed into the reference tree (VOLK is not
-// installed in this image). It declares the kernels the reference headers call with VOLK's
-// published signatures (volk 2.x: volk_complex.h's lv_32fc_t = std::complex<float>); nothing here is
-// defined, linked or executed, so it proves that the overlay and its callers type-check against the
-// reference's block API -- never any arithmetic.
+// Declaration-only stand-in for VOLK's public header (VOLK is not installed in this image). It declares
+// the kernels the reference headers call with VOLK's published signatures (volk 2.x: volk_complex.h's
+// lv_32fc_t = std::complex<float>); nothing is defined here. Two users:
+// * the overlay tests (tests/test_overlay_syntax.py, test_ifnr_overlay.py, test_symsync_overlay.py) run
+//   `g++ -fsyntax-only` over the drop-in overlay placed into the reference tree: that proves the overlay
+//   and its callers type-check against the reference's block API -- never any arithmetic;
+// * oracle/ref_blocks.cpp compiles the reference's own block headers against these declarations and
+//   links oracle/ref_standins.cpp, which defines the few kernels those headers call as scalar loops.
+//   That probe does run, and its arithmetic is what tests/golden/ref_blocks_*.npz record.
 #pragma once
 #include <complex>
 #include <cstddef>

@@ -28,7 +28,7 @@ import pytest
 import sdrpp_amd
 from sdrpp_amd import dsp
 from _util import fir_atol, write_report
-from test_symsync import same, shaped_psk, gfsk_signal, errors_at_best_lag, quadrant, ref_slicer, GFSK_ARGS
+from _restated import same, shaped_psk, gfsk_signal, errors_at_best_lag, quadrant, ref_slicer, GFSK_ARGS
 
 pytestmark = pytest.mark.gpu
 

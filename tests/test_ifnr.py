@@ -1,6 +1,8 @@
 """IF noise reduction on the device: noise_reduction::FMIF, NoiseBlanker and Squelch (libsdrgpu,
-HIP) against numpy restatements of fm_if.h:45-77, noise_blanker.h:38-57 and squelch.h:33-63 (FFTW
-and VOLK are absent, so the reference's own headers cannot be compiled).
+HIP) against numpy restatements of fm_if.h:45-77, noise_blanker.h:38-57 and squelch.h:33-63
+(tests/_restated.py). The restatements and the FMIF bar are themselves held to the reference's own
+headers, compiled over scalar stand-ins for VOLK and FFTW (oracle/ref_blocks.cpp), by
+tests/test_ref_blocks.py.
 
 Bars:
 * FMIF -- the FIR bar of tests/_util.py: atol = 8 eps32 sqrt(B) sum|w| max|x| against an fp64
@@ -19,6 +21,8 @@ import pytest
 import sdrpp_amd
 from sdrpp_amd import dsp
 from _util import EPS32, iq
+from _restated import (fmif_cuts, fm_two_tone, fmif_inputs, fmif_atol, fmif_check, bursty, NoiseBlankerRef, SquelchRef,
+                       noise_at, SQ_SEQUENCE)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,80 +33,6 @@ def _need_gpu():
 
 
 # ------------------------------------------------------------------ FMIF
-N_FMIF = 12000
-
-
-def fmif_cuts(B):
-    cuts = [1, B - 2, B - 1, B, 0, 1023, 1024, 1025, 4097]
-    return cuts + [N_FMIF - sum(cuts)]
-
-
-def fm_two_tone(rng, n):
-    """Two-tone FM at 75 kHz deviation, fs = 250 kHz, -20 dB Gaussian noise, 200 exact zeros."""
-    fs = 250e3
-    t = np.arange(n) / fs
-    m = 0.5 * np.sin(2 * np.pi * 1000.0 * t) + 0.5 * np.sin(2 * np.pi * 3000.0 * t)
-    x = np.exp(1j * 2 * np.pi * 75e3 * np.cumsum(m) / fs)
-    x = x + 0.1 * (rng.standard_normal(n) + 1j * rng.standard_normal(n)) / np.sqrt(2.0)
-    x = x.astype(np.complex64)
-    x[n // 2:n // 2 + 200] = 0
-    return x
-
-
-def fmif_inputs(kind, seed=20240607):
-    rng = np.random.default_rng(seed)   # local: the preconditions below do not depend on test order
-    return fm_two_tone(rng, N_FMIF) if kind == "fm" else iq(rng, N_FMIF)
-
-
-def fmif_spectra(x, B, hist=None):
-    """X_i[k] of fm_if.h:52-55 in fp64: [i, k] over the stream with B - 1 zeros (or hist) in front."""
-    w = dsp.fmif_window(B).astype(np.float64)
-    h = np.zeros(B - 1, np.complex128) if hist is None else np.asarray(hist, np.complex128)
-    buf = np.concatenate([h, np.asarray(x).astype(np.complex128)])
-    win = np.lib.stride_tricks.sliding_window_view(buf, B)
-    return np.fft.fft(win * w, axis=1), np.all(win == 0, axis=1)
-
-
-def fmif_atol(B, x):
-    w = dsp.fmif_window(B)
-    return 8 * EPS32 * np.sqrt(B) * np.abs(w.astype(np.float64)).sum() * np.abs(x).max()
-
-
-def fmif_check(out, x, B, what):
-    """The FMIF bar (module docstring); returns the undecidable share."""
-    X, allzero = fmif_spectra(x, B)
-    n = len(x)
-    assert out.shape == (n,)
-    atol = fmif_atol(B, x)
-    k = np.arange(B)
-    vals = X * np.exp(2j * np.pi * k * (B // 2) / B)       # every bin's value at sample B/2 of the back transform
-    mag = np.abs(X)
-    idx = np.argmax(mag, axis=1)                             # first maximum = lowest k
-    top = np.sort(mag, axis=1)
-    decidable = (top[:, -1] - top[:, -2]) >= 2 * atol
-    ref = vals[np.arange(n), idx]
-    ref[allzero] = 0
-    err = np.abs(out.astype(np.complex128) - ref)
-    # Also strict: samples whose near-maximum bins all carry the SAME output value (apart by less
-    # than fp32 resolution), so no tie-break can show. At B = 3 that is every sample: nuttall(n, 2)
-    # is (0, 1, 0), all three bins have magnitude |x[i-1]| and value x[i-1], and without this the
-    # reference alone would count as 100 % undecidable.
-    near = mag >= (top[:, -1] - 2 * atol)[:, None]
-    spread = np.where(near, np.abs(vals - ref[:, None]), 0.0).max(axis=1)
-    same_value = spread <= EPS32 * np.abs(ref)
-    strict = decidable | allzero | same_value
-    print(f"{what}: atol {atol:.3e}, decidable max err {err[strict].max():.3e} ({err[strict].max() / atol:.3f} atol), "
-          f"undecidable {np.mean(~strict):.4%}")
-    assert err[strict].max() <= atol, f"{what}: decidable samples, max err {err[strict].max():.3e} > atol {atol:.3e}"
-    rest = np.flatnonzero(~strict)
-    if rest.size:
-        d = np.abs(out[rest].astype(np.complex128)[:, None] - vals[rest])
-        best = np.where(near[rest], d, np.inf).min(axis=1)
-        print(f"{what}: undecidable max err to a near-maximum bin {best.max():.3e}")
-        assert best.max() <= atol, f"{what}: undecidable samples, {best.max():.3e} > atol {atol:.3e}"
-    return float(np.mean(~strict))
-
-
 def run_cut(blk, x, cuts):
     outs, i = [], 0
     for c in cuts:
@@ -157,48 +87,6 @@ def test_fmif_passes_an_on_bin_tone():
 
 
 # ------------------------------------------------------------------ NoiseBlanker
-def bursty(rng, n):
-    """Level steps over 60 dB, a run of exact zeros and single-sample spikes x50 (as test_loops.py)."""
-    env = np.repeat(10.0 ** rng.uniform(-3, 0, n // 500 + 1), 500)[:n]
-    x = (iq(rng, n) * env.astype(np.float32)).astype(np.complex64)
-    x[n // 3:n // 3 + 700] = 0
-    x[rng.integers(0, n, 12)] *= 50
-    return x
-
-
-class NoiseBlankerRef:
-    """noise_blanker.h:38-57 over np.float32 scalars, operation for operation."""
-
-    def __init__(self, rate, level):
-        self.amp = np.float32(1.0)
-        self.set(rate, level)
-
-    def set(self, rate, level):
-        self.rate = np.float32(rate)
-        self.inv = np.float32(1.0) - self.rate
-        self.level = np.float32(level)
-
-    def reset(self):
-        self.amp = np.float32(1.0)
-
-    def process(self, x):
-        re, im = x.real.astype(np.float32), x.imag.astype(np.float32)
-        a = np.sqrt((re * re) + (im * im))                  # complex_t::amplitude(), f32 throughout
-        g = np.ones(len(x), np.float32)
-        amp, rate, inv, level, one = self.amp, self.rate, self.inv, self.level, np.float32(1.0)
-        for i in range(len(x)):
-            ia = a[i]
-            if ia != 0:
-                amp = (amp * inv) + (ia * rate)
-                excess = ia / amp
-                if excess > level:
-                    g[i] = one / excess
-        self.amp = amp
-        out = np.empty(len(x), np.complex64)
-        out.real, out.imag = re * g, im * g
-        return out
-
-
 def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
@@ -235,42 +123,6 @@ def test_noise_blanker_set_keeps_amp_and_reset_restores_it():
 
 
 # ------------------------------------------------------------------ Squelch
-SQ_N = 1000
-
-
-class SquelchRef:
-    """squelch.h:33-63 with the level kept in fp64; cnt per object (the port's deliberate deviation)."""
-
-    def __init__(self, level):
-        self.L = float(np.float32(level))
-        self.muted, self.cnt = False, 0
-        self.levels = []
-
-    def set_level(self, level):
-        self.L = float(np.float32(level))
-
-    def process(self, x):
-        level = 20.0 * np.log10(np.abs(x.astype(np.complex128)).sum() / len(x))
-        self.levels.append((level, self.L))
-        if self.muted:
-            if level < self.L or self.cnt <= 0:
-                self.cnt = 10
-            else:
-                self.cnt -= 1
-                if self.cnt == 0:
-                    self.muted = False
-        elif level < self.L - 1.0:
-            self.cnt = 0
-            self.muted = True
-        return np.zeros_like(x) if self.muted else x.copy()
-
-
-def noise_at(rng, db):
-    x = (rng.standard_normal(SQ_N) + 1j * rng.standard_normal(SQ_N)) / np.sqrt(2.0)
-    x *= 10.0 ** (db / 20.0) / np.abs(x).mean()
-    return x.astype(np.complex64)
-
-
 def squelch_run(g, r, blocks):
     for j, x in enumerate(blocks):
         a, b = g.process(x), r.process(x)
@@ -279,9 +131,6 @@ def squelch_run(g, r, blocks):
         assert min(abs(level - L), abs(level - (L - 1.0))) >= 0.05, (j, level, L)
         assert same_bits(a, b), f"block {j} (level {level:.2f} dB): expected {'zeros' if r.muted else 'the input'}"
         assert g.is_muted() == r.muted, j
-
-
-SQ_SEQUENCE = [-20.0, -45.0] + [-20.0] * 10 + [-20.0, -30.5, -45.0] + [-20.0] * 3 + [-40.0] + [-20.0] * 11
 
 
 def test_squelch_sequence():

@@ -185,7 +185,7 @@ CHUNK_CUTS = [1, 1023, 1024, 1025, 0, 2049, 37]
 def _chunk_edge_cases():
     """(name, block, oracle, stream): each serial block with the oracle its own bit-exact test uses, on
     sum(CHUNK_CUTS) samples from a generator of this test's own (the session `rng` is not advanced)."""
-    from test_ifnr import NoiseBlankerRef, bursty as if_bursty
+    from _restated import NoiseBlankerRef, bursty as if_bursty
     rng = np.random.default_rng(0x10C5)
     n = sum(CHUNK_CUTS)
     rate = 10.0 / 48000

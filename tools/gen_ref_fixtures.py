@@ -1,20 +1,222 @@
-"""Fixtures produced by the REFERENCE's own code (oracle/_ref/ref_probe, compiled from the
-reference tree's header-only window/math/types/taps headers): run in the dev container where
-/root/reference exists; the outputs are committed under tests/golden/ref_*.npz so the GPU box
-(which has no reference tree) checks against them."""
+"""Fixtures produced by the REFERENCE's own code: run in the dev container where the reference tree
+exists; the outputs are committed under tests/golden/ref_*.npz so the GPU box (which has no reference
+tree) checks against them.
+
+* oracle/_ref/ref_probe -- the header-only window/math/types/taps headers: ref_windows.npz,
+  ref_taps.npz, ref_quad.npz.
+* oracle/_ref/ref_blocks (and ref_blocks_sum4, the same with 4-lane summation order) -- the stateful
+  blocks and chains: ref_blocks_*.npz, one file per group of blocks, each holding the seeded inputs,
+  the parameters and the reference outputs. `blocks_fixtures()` builds them in memory;
+  tests/test_ref_blocks.py calls it to require that a fresh build reproduces the committed files."""
 import hashlib
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE = os.path.join(ROOT, "oracle", "_ref", "ref_probe")
+BLOCKS = os.path.join(ROOT, "oracle", "_ref", "ref_blocks")
 OUT = os.path.join(ROOT, "tests", "golden")
+MAX_BYTES = 709691          # the largest fixture under tests/golden before these (fft_aes17.npz)
 
 
 def probe(*args, stdin=None):
     return subprocess.run([PROBE, *map(str, args)], input=stdin, capture_output=True, check=True).stdout
+
+
+def num(v):
+    return v if isinstance(v, str) else (str(v) if isinstance(v, (int, np.integer)) else f"{float(v):.17g}")
+
+
+def blocks(mode, calls, params, x, out_dtype, sum4=False, second=False):
+    """One run of ref_blocks: (int32 counts per process() call, outputs[, the rds mode's bits])."""
+    calls = ",".join(num(c) for c in calls) if not isinstance(calls, str) else calls
+    raw = subprocess.run([BLOCKS + ("_sum4" if sum4 else ""), mode, calls, *map(num, params)],
+                         input=np.ascontiguousarray(x).tobytes(), capture_output=True, check=True).stdout
+    nc = int(np.frombuffer(raw[:4], np.int32)[0])
+    counts = np.frombuffer(raw[4:4 + 4 * nc], np.int32)
+    total = int(counts.sum())
+    size = np.dtype(out_dtype).itemsize
+    y = np.frombuffer(raw[4 + 4 * nc:4 + 4 * nc + total * size], out_dtype)
+    rest = raw[4 + 4 * nc + total * size:]
+    if second:
+        assert len(rest) == total
+        return counts, y, np.frombuffer(rest, np.uint8)
+    assert not rest
+    return counts, y
+
+
+def design(mode, *params):
+    return np.frombuffer(subprocess.run([BLOCKS, mode, "0", *map(num, params)], capture_output=True, check=True).stdout,
+                         np.float32)
+
+
+def whole_and_cut(mode, params, x, out_dtype, cuts, may_differ=False):
+    """The reference fed in one call and in `cuts`. Same-rate blocks other than loop::AGC (whose clip
+    look-ahead ends at the call) give the same output either way: then only one copy is kept."""
+    cw, yw = blocks(mode, [len(x)], params, x, out_dtype)
+    cc, yc = blocks(mode, cuts, params, x, out_dtype)
+    assert sum(cuts) == len(x) and len(cc) == len(cuts)
+    if not may_differ:
+        assert yw.tobytes() == yc.tobytes(), mode
+    return cw, yw, cc, yc
+
+
+def blocks_fixtures():
+    """{file name: {key: array}} of every ref_blocks_*.npz."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import _restated as R
+    f32, c64 = np.float32, np.complex64
+    N, CUTS = R.N, R.CUTS
+    files = {}
+
+    # ---- FastAGC, slicer, differential decoder, MM
+    g = {"cuts": np.array(CUTS, np.int32)}
+    x = R.shaped_psk(11, 4, amp=0.05)[0]
+    x[5000:5100] = 0                                            # the gain runs into maxGain
+    g["fastagc_params"] = np.array([1.0, 50.0, 0.1, 2.0])
+    g["fastagc_x"] = x
+    g["fastagc_y_c"] = whole_and_cut("fastagc_c", g["fastagc_params"], x, c64, CUTS)[1]
+    g["fastagc_y_f"] = whole_and_cut("fastagc_f", g["fastagc_params"], np.ascontiguousarray(x.real), f32, CUTS)[1]
+    x = R.noise(5, False)
+    x[::7] = 0.0
+    x[3] = -0.0
+    g["slicer_x"] = x
+    g["slicer_y"] = whole_and_cut("slicer", [], x, np.uint8, CUTS)[1]
+    for modulus, init in [(2, 0), (4, 3)]:
+        x = np.random.default_rng(modulus).integers(0, modulus, N).astype(np.uint8)
+        g[f"diff{modulus}_x"] = x
+        g[f"diff{modulus}_init"] = np.array(init)
+        g[f"diff{modulus}_y"] = whole_and_cut("diff", [modulus, init], x, np.uint8, CUTS)[1]
+    files["ref_blocks_sym.npz"] = g
+
+    g = {"cuts": np.array(CUTS, np.int32)}
+    om2 = 5000.0 / 1187.5
+    for cplx in (False, True):
+        t, mode, dt = ("c", "mm_c", c64) if cplx else ("f", "mm_f", f32)
+        g[f"x_psk_{t}"], g[f"x_noise_{t}"] = R.mm_input("psk", cplx), R.mm_input("noise", cplx)
+        # c: gains and a limit at which omega runs into both ends of [omega (1 - rel), omega (1 + rel)]
+        for name, kind, params in [("a", "psk", (4.0, 2.5e-5, 0.01, 0.01)), ("b", "noise", (om2, 1e-6, 0.01, 0.01)),
+                                   ("c", "noise", (4.0, 5e-3, 0.05, 0.002))]:
+            x = g[f"x_{kind}_{t}"]
+            cw, yw, cc, yc = whole_and_cut(mode, params, x, dt, CUTS, may_differ=True)
+            assert yw.tobytes() == yc.tobytes()
+            g[f"mm_{name}_{t}_params"], g[f"mm_{name}_{t}_y"], g[f"mm_{name}_{t}_cut_counts"] = np.array(params), yw, cc
+        # setInterpParams(64, 8) before the first sample
+        x = g[f"x_psk_{t}"]
+        c, y = blocks(mode, f"i64x8,{N}", (4.0, 2.5e-5, 0.01, 0.01), x, dt)
+        g[f"mm_interp64_{t}_y"] = y
+        # 3001 samples, reset(), 2999 samples, setOmega(5000 / 1187.5), 6000 samples
+        c, y = blocks(mode, f"3001,r,2999,o{om2:.17g},6000", (4.0, 2.5e-5, 0.01, 0.01), x, dt)
+        g[f"mm_ops_{t}_counts"], g[f"mm_ops_{t}_y"] = c, y
+    g["mm_ops_omega2"] = np.array(om2)
+    files["ref_blocks_mm.npz"] = g
+
+    # ---- Costas: seed 0 of each configuration of tests/test_symsync.py
+    for fname, cases in [("ref_blocks_costas_a.npz", ("order2", "order4")), ("ref_blocks_costas_b.npz", ("order8", "rds_second_loop"))]:
+        g = {"cuts": np.array(CUTS, np.int32)}
+        for case in cases:
+            c = R.COSTAS_CASES[case]
+            kw = c["kw"]
+            params = [c["order"], c["bandwidth"]]
+            if kw:
+                params += [kw["init_phase"], kw["init_freq"], kw["min_freq"], kw["max_freq"]]
+            x = R.costas_input(case, 0)
+            g[f"{case}_x"] = x
+            g[f"{case}_y"] = whole_and_cut("costas", params, x, c64, CUTS)[1]
+        files[fname] = g
+
+    # ---- IF noise reduction
+    g = {"cuts": np.array(CUTS, np.int32)}
+    x = R.bursty(np.random.default_rng(77), N)
+    g["nb_x"] = x
+    for k, (rate, level) in enumerate([(500.0 / 24000.0, 10.0), (500.0 / 250000.0, 2.0)]):
+        g[f"nb{k}_params"] = np.array([rate, level])
+        g[f"nb{k}_y"] = whole_and_cut("nb", (rate, level), x, c64, CUTS)[1]
+    blk = R.squelch_blocks()
+    x = np.concatenate(blk)
+    c, y = blocks("squelch", [len(b) for b in blk], [-30.0], x, c64)
+    y = y.reshape(len(blk), -1)
+    is_open = np.array([bool(np.any(r != 0)) for r in y])
+    for j, b in enumerate(blk):                                 # each block: the input, or zeros
+        assert y[j].tobytes() == (b if is_open[j] else np.zeros_like(b)).tobytes()
+    g["squelch_level"], g["squelch_x"], g["squelch_open"] = np.array(-30.0), x.reshape(len(blk), -1), is_open
+    for kind in ("fm", "uniform"):
+        x = R.fmif_inputs(kind, n=3000)
+        g[f"fmif_x_{kind}"] = x
+        for B in (3, 16, 31):
+            g[f"fmif_y_{kind}_{B}"] = whole_and_cut("fmif", [B], x, c64, R.fmif_cuts(B, 3000))[1]
+    files["ref_blocks_ifnr.npz"] = g
+
+    # ---- the C oracle's loops: AGC, DC blocker, de-emphasis
+    g = {"cuts": np.array(CUTS, np.int32)}
+    xc = R.bursty(np.random.default_rng(0x10C5), N)
+    xf = np.ascontiguousarray(xc.real)
+    g["x_c"], g["x_f"] = xc, xf
+    agc = (1.0, 50.0 / 48000, 5.0 / 48000, 10e6, 10.0, "inf")
+    g["agc_params"] = np.array([float(v) for v in agc])
+    for t, x, dt in (("f", xf, f32), ("c", xc, c64)):
+        _, yw, _, yc = whole_and_cut("agc_" + t, agc, x, dt, CUTS, may_differ=True)   # the look-ahead ends at the call
+        g[f"agc_{t}_y"], g[f"agc_{t}_y_cut"] = yw, yc
+    files["ref_blocks_loops_a.npz"] = g
+    g = {"cuts": np.array(CUTS, np.int32)}
+    rate = 10.0 / 48000
+    g["dcb_rate"] = np.array(rate)
+    xc, xf = (xc + c64(0.3 + 0.2j)).astype(c64), (xf + f32(0.25)).astype(f32)   # a DC level for the blocker to find
+    g["x_c"], g["x_f"] = xc, xf
+    g["dcb_c_y"] = whole_and_cut("dcb_c", [rate], xc, c64, CUTS)[1]
+    g["dcb_f_y"] = whole_and_cut("dcb_f", [rate], xf, f32, CUTS)[1]
+    g["deemp_params"] = np.array([50e-6, 48000.0])
+    g["deemp_f_y"] = whole_and_cut("deemp_f", g["deemp_params"], xf, f32, CUTS)[1]
+    g["deemp_s_y"] = whole_and_cut("deemp_s", g["deemp_params"], xc, c64, CUTS)[1]   # stereo_t pairs as (l, r) = (re, im)
+    files["ref_blocks_loops_b.npz"] = g
+
+    # ---- host design code
+    g = {}
+    for count, beta, Ts in [(31, 0.6, 4.0), (33, 0.5, 4.0), (64, 0.35, 8.0), (101, 1.0, 5000.0 / 1187.5)]:
+        g[f"rrc_{count}_{beta}_{Ts:.6g}"] = design("rrc", count, beta, Ts)
+        g[f"rrc_{count}_{beta}_{Ts:.6g}_args"] = np.array([count, beta, Ts])
+    for P, T in [(128, 8), (64, 8), (4, 3)]:
+        g[f"mmbank_{P}_{T}"] = design("mmbank", P, T).reshape(P, T)
+    for B in (3, 9, 15, 16, 31, 32):
+        g[f"fmifwin_{B}"] = design("fmifwin", B)
+    files["ref_blocks_design.npz"] = g
+
+    # ---- chains on the known-answer signals, both builds (ascending order and 4-lane sums)
+    S = CHAIN_SIGNALS
+    chains = {
+        "psk2": ("psk", (2,) + R.PSK_ARGS, R.shaped_psk(*S["psk2"], 2, amp=0.05)[0], c64),
+        "psk4": ("psk", (4,) + R.PSK_ARGS, R.shaped_psk(*S["psk4"], 4, amp=0.05)[0], c64),
+        "gfsk": ("gfsk", R.GFSK_ARGS, R.gfsk_signal(*S["gfsk"])[0], f32),
+        "rds0": ("rds", (), R.rds_signal(*S["rds0"])[0], f32),
+        "rds1": ("rds", (), R.rds_signal(*S["rds1"])[0], f32),
+    }
+    for fname, names in [("ref_blocks_chains_a.npz", ("psk2", "psk4", "gfsk")), ("ref_blocks_chains_b.npz", ("rds0", "rds1"))]:
+        g = {"cuts": np.array(CUTS, np.int32)}
+        for name in names:
+            mode, params, x, dt = chains[name]
+            g[f"{name}_x"], g[f"{name}_signal"] = x, np.array(S[name], np.float64)
+            if params:
+                g[f"{name}_params"] = np.array(params, np.float64)
+            for sum4, tag in ((False, "y"), (True, "y_sum4")):
+                whole = blocks(mode, [N], params, x, dt, sum4=sum4, second=mode == "rds")
+                cut = blocks(mode, CUTS, params, x, dt, sum4=sum4, second=mode == "rds")
+                assert all(a.tobytes() == b.tobytes() for a, b in zip(whole[1:], cut[1:])), name
+                g[f"{name}_{tag}"] = whole[1]
+                if mode == "rds":
+                    g[f"{name}_{tag.replace('y', 'bits')}"] = whole[2]
+            g[f"{name}_cut_counts"] = cut[0]
+        files[fname] = g
+    return files
+
+
+# Known-answer signals of the chain fixtures: the seed of shaped_psk / gfsk_signal, (f0, snr_db, seed) of
+# rds_signal. tests/test_ref_blocks.py test_chain_inputs_meet_the_preconditions states the conditions they
+# are chosen to meet (both builds decide alike, no symbol within the comparison bar of a decision boundary,
+# no symbol's interpolator branch undecided).
+CHAIN_SIGNALS = {"psk2": (73,), "psk4": (72,), "gfsk": (56,), "rds0": (2.0, 30.0, 62), "rds1": (-5.0, 20.0, 51)}
 
 
 def main():
@@ -45,6 +247,12 @@ def main():
     offs = np.array([2 * np.pi * (-1.5e6 / 61.44e6), 2 * np.pi * (-2.5e6 / 61.44e6), 2 * np.pi * (2.5e6 / 61.44e6)])
     deltas = np.stack([np.frombuffer(probe("xlatordelta", f"{float(o):.17g}"), np.float32) for o in offs])
     np.savez_compressed(os.path.join(OUT, "ref_quad.npz"), x=x, dev=dev, y=y, offs=offs, deltas=deltas)
+    for fname, arrays in blocks_fixtures().items():
+        path = os.path.join(OUT, fname)
+        np.savez_compressed(path, **arrays)
+        size = os.path.getsize(path)
+        assert size <= MAX_BYTES, f"{fname}: {size} bytes > {MAX_BYTES}"
+        print(f"{fname}: {size} bytes")
     print("reference-code fixtures written")
 
 
