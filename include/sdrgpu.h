@@ -342,7 +342,7 @@ int sdrgpu_block_destroy(sdrgpu_block* h);
  * `frames` rows; state and history stay on the device, and results do not depend on how the rows are
  * cut into calls. The loops (FastAGC, Costas, MM) run one lane per stream, 64 streams per wave, on the
  * per-sample steps of the single-stream kernels: every column is bit-identical to the single-stream
- * block fed that column. Parameters are fixed at creation.
+ * block fed that column. Parameters are fixed at creation (sdrgpu_bank_agc_set_gain excepted).
  * Every create function takes (handle, device, streams, the arguments of the single-stream create
  * function in its order) and applies that function's checks; streams < 1 is SDRGPU_EARG. All checks run
  * before the device is selected. frames * streams beyond INT_MAX (the kernels' index type) is
@@ -381,6 +381,42 @@ int sdrgpu_bank_psk_create(sdrgpu_bank** h, int device, int streams, int order, 
  * FIR(rootRaisedCosine) -> bank MM<float>; C64 -> F32 soft symbols */
 int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate, double deviation,
                             int rrcTapCount, double rrcBeta, double omegaGain, double muGain, double omegaRelLimit);
+
+/* -- analogue receiver banks: a channelizer's rows to squelched AM / NFM audio per channel.
+ * The AGC, the DC blocker and the de-emphasis run one lane per stream on the per-sample steps of the
+ * single-stream kernels: every column is bit-identical to the single-stream block fed that column in
+ * the same calls. Every call is asynchronous on its stream; a call of 0 frames changes nothing. */
+/* loop::AGC<T> per stream (loop/agc.h:13-147), dtype F32 or C64; `enabled` 0 is the fixed-gain limiter
+ * (agc.h:127-141, the branch AM's OFF mode runs). The clip look-ahead (agc.h:109-118) is the maximum of |x|
+ * from the sample to the end of the CALL for that stream, as in the reference: results depend on where
+ * calls end, exactly as sdrgpu_agc_create's do. reset -> amp = setPoint / initGain, gain = min(maxGain, initGain) */
+int sdrgpu_bank_agc_create(sdrgpu_bank** h, int device, int streams, int dtype, double setPoint, double attack, double decay,
+                           double maxGain, double maxOutputAmp, double initGain, int enabled);
+/* AGC::setGain (agc.h:31-35) for all streams, latched at the next call with rows; also on a
+ * sdrgpu_bank_am_create handle (the last AGC of the chain: its audio AGC); SDRGPU_ESTATE without an AGC */
+int sdrgpu_bank_agc_set_gain(sdrgpu_bank* h, float gain);
+/* correction::DCBlocker<T> per stream (correction/dc_blocker.h:54-60), dtype F32 or C64; offset 0 at create / reset */
+int sdrgpu_bank_dc_blocker_create(sdrgpu_bank** h, int device, int streams, int dtype, double rate);
+/* filter::Deemphasis<float> per stream (filter/deephasis.h:58-65, 91-94); F32; alpha as sdrgpu_deemphasis_create */
+int sdrgpu_bank_deemphasis_create(sdrgpu_bank** h, int device, int streams, double tau, double samplerate);
+/* noise_reduction::Squelch per stream (noise_reduction/squelch.h:33-63); C64 -> C64. Per call and stream:
+ * 20 log10f(mean |x| over the call's rows), the mute state machine (10 calls above the level before
+ * unmute, 1 dB hysteresis) with a count per stream, and the row copied or zeroed. A stream's rows are
+ * summed in an order that depends on `frames` alone (32-row tiles in ascending rows, then the tiles in
+ * ascending order): not the order of sdrgpu_squelch_create, so a level within rounding of a threshold may
+ * decide differently. */
+int sdrgpu_bank_squelch_create(sdrgpu_bank** h, int device, int streams, double level);
+int sdrgpu_bank_squelch_muted(sdrgpu_bank* h, int* muted);   /* muted[S] after the last call (synchronises) */
+/* demod::FM<float> per stream (demod/fm.h:25-44, 86-93, 117-145): bank Quadrature(bandwidth / 2 at
+ * samplerate) -> bank FIR of the taps of sdrgpu_fm_create (low, high or band pass; none with both flags
+ * off); C64 -> F32 mono; bit-identical to those banks run one after another */
+int sdrgpu_bank_fm_create(sdrgpu_bank** h, int device, int streams, double samplerate, double bandwidth, int lowPass, int highPass);
+/* demod::AM<float> per stream (demod/am.h:28-49, 114-131): agcMode 0 OFF, 1 CARRIER, 2 AUDIO;
+ * [CARRIER: bank AGC<C64>(1, attack, decay, 10e6, 10, inf)] -> |x| (volk_32fc_magnitude_32f) -> bank
+ * DCBlocker -> [not CARRIER: bank AGC<F32>, enabled iff AUDIO] -> bank FIR(lowPass(bandwidth / 2,
+ * 0.1 bandwidth / 2, samplerate)); C64 -> F32 mono; bit-identical to those banks run one after another */
+int sdrgpu_bank_am_create(sdrgpu_bank** h, int device, int streams, int agcMode, double bandwidth, double agcAttack,
+                          double agcDecay, double dcBlockRate, double samplerate);
 
 /* device buffers of frames * S (in) and sdrgpu_bank_out_rows(frames) * S (out) elements, on `stream` (0:
  * the handle's own); asynchronous except for a bank that ends in MM (above). Returns the rows written. */

@@ -172,6 +172,14 @@ def _load():
         "sdrgpu_bank_mm_create": (i, [pp, i, i, i, d, d, d, d, i, i]),
         "sdrgpu_bank_psk_create": (i, [pp, i, i, i, d, d, i, d, d, d, d, d, d]),
         "sdrgpu_bank_gfsk_create": (i, [pp, i, i, d, d, d, i, d, d, d, d]),
+        "sdrgpu_bank_agc_create": (i, [pp, i, i, i, d, d, d, d, d, d, i]),
+        "sdrgpu_bank_agc_set_gain": (i, [vp, ctypes.c_float]),
+        "sdrgpu_bank_dc_blocker_create": (i, [pp, i, i, i, d]),
+        "sdrgpu_bank_deemphasis_create": (i, [pp, i, i, d, d]),
+        "sdrgpu_bank_squelch_create": (i, [pp, i, i, d]),
+        "sdrgpu_bank_squelch_muted": (i, [vp, ctypes.POINTER(i)]),
+        "sdrgpu_bank_fm_create": (i, [pp, i, i, d, d, i, i]),
+        "sdrgpu_bank_am_create": (i, [pp, i, i, i, d, d, d, d, d]),
         "sdrgpu_bank_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_bank_process": (i, [vp, vp, i, vp]),
         "sdrgpu_bank_out_rows": (i, [vp, i]),

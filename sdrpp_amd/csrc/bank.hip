@@ -3,7 +3,10 @@
 // parameters, element m of stream k at x[m * S + k], one launch per block and call.
 //   BankQuad, BankFir        demod::Quadrature, filter::FIR<D, float> per stream
 //   BankFastAgc, BankCostas, BankMm   loop::FastAGC<T>, loop::Costas<ORDER>, clock_recovery::MM<T> per stream
-//   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip)
+//   BankAgc, BankDcb, BankDeemp      loop::AGC<T>, correction::DCBlocker<T>, filter::Deemphasis<float> per stream
+//   BankSquelch, BankMag     noise_reduction::Squelch per stream; volk_32fc_magnitude_32f over the flat stream
+//   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip),
+//                            demod::FM<float> / demod::AM<float> per stream (those of blocks.hip / loops.hip)
 // Top to bottom: the Bank base and its handle, the blocks (each: configure = the argument checks and the
 // parameters, host only; init = device state; reset; run = its launch), the C entry points.
 // A create function checks every argument (configure, of a chain: of all its stages) before it selects
@@ -11,11 +14,13 @@
 // nothing of rows.
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
 #include "sdrgpu_internal.h"
 #include "bank_kernels.h"
+#include "bank_audio_kernels.h"
 #include "blocks.h"
 #include "symsync_args.h"
 
@@ -274,6 +279,162 @@ struct BankMm : Bank {
     }
 };
 
+// ------------------------------------------------------------------------- AGC
+// tiles x waves, folded into grid.x (bank_tile_of_block)
+static dim3 tiles_by_waves(int frames, int S) { return dim3((unsigned)((frames + BANK_F - 1) / BANK_F) * waves_of(S).x); }
+
+struct BankAgc : Bank {
+    AgcParams p{};
+    float initGain = 1.0f;
+    DevBuf state, tm;   // amp[S], gain[S]; the tile maxima of a call (grows on demand)
+    bool pending = false;
+    float pendingGain = 0.0f;
+    int configure(int streams, int dtype, double setPoint, double attack, double decay, double maxGain, double maxOutputAmp,
+                  double initGain_, int enabled) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype)) { set_error("bank_agc: dtype %d not F32 / C64", dtype); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        p.setPoint = (float)setPoint;   // AGC::init (agc.h:13-26): members are float
+        p.attack = (float)attack;
+        p.invAttack = 1.0f - p.attack;
+        p.decay = (float)decay;
+        p.invDecay = 1.0f - p.decay;
+        p.maxGain = (float)maxGain;
+        p.maxOutputAmp = (float)maxOutputAmp;
+        p.enabled = enabled ? 1 : 0;
+        initGain = (float)initGain_;
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override {   // agc.h:81-86
+        std::vector<float> st(2 * (size_t)S, p.setPoint / initGain);
+        std::fill(st.begin() + S, st.end(), (p.maxGain < initGain) ? p.maxGain : initGain);
+        pending = false;
+        return upload(state, st);
+    }
+    void set_gain(float g) {   // agc.h:31-35, latched by the next call that has rows
+        pending = true;
+        pendingGain = g;
+    }
+    template <typename DT>
+    void run_t(const void* in, int frames, void* out, hipStream_t s) {
+        if (p.enabled)
+            hipLaunchKernelGGL(bank_tile_max_kernel<DT>, tiles_by_waves(frames, S), dim3(BANK_W), 0, s, (const DT*)in, frames, S,
+                               tm.as<float>());
+        hipLaunchKernelGGL(bank_agc_kernel<DT>, waves_of(S), dim3(BANK_W), 0, s, (const DT*)in, (DT*)out, frames, S, p,
+                           state.as<float>(), tm.as<float>(), pending ? 1 : 0, pendingGain);
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        if (p.enabled) SDRGPU_CHECK(tm.ensure(sizeof(float) * (size_t)((frames + BANK_F - 1) / BANK_F) * S));
+        if (in_dtype == SDRGPU_C64) run_t<float2>(in, frames, out, s);
+        else run_t<float>(in, frames, out, s);
+        SDRGPU_HIP(hipGetLastError());
+        pending = false;
+        return frames;
+    }
+};
+
+// ------------------------------------------------------------------- DCBlocker
+struct BankDcb : Bank {
+    float rate = 0.0f;
+    DevBuf state;   // offset[S] (C64: re[S], im[S])
+    int configure(int streams, int dtype, double rate_) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype)) { set_error("bank_dc_blocker: dtype %d not F32 / C64", dtype); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        rate = (float)rate_;
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override { return upload(state, std::vector<float>(2 * (size_t)S, 0.0f)); }   // dc_blocker.h:45-48
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        if (in_dtype == SDRGPU_C64)
+            hipLaunchKernelGGL(bank_dcb_kernel<float2>, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S, rate,
+                               state.as<float>());
+        else
+            hipLaunchKernelGGL(bank_dcb_kernel<float>, waves_of(S), dim3(BANK_W), 0, s, (const float*)in, (float*)out, frames, S, rate,
+                               state.as<float>());
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// ------------------------------------------------------------------ Deemphasis
+struct BankDeemp : Bank {
+    float alpha = 1.0f;
+    DevBuf state;   // lastOut[S]
+    int configure(int streams, double tau, double samplerate) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!(samplerate > 0)) { set_error("bank_deemphasis: samplerate %g not positive", samplerate); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = out_dtype = SDRGPU_F32;
+        const float dt = (float)(1.0f / samplerate);   // updateAlpha (deephasis.h:91-94), as sdrgpu_deemphasis_create
+        alpha = (float)((double)dt / (tau + (double)dt));
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override { return upload(state, std::vector<float>(S, 0.0f)); }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        hipLaunchKernelGGL(bank_deemp_kernel, waves_of(S), dim3(BANK_W), 0, s, (const float*)in, (float*)out, frames, S, alpha,
+                           state.as<float>());
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// --------------------------------------------------------------------- Squelch
+struct BankSquelch : Bank {
+    float level = -50.0f;
+    DevBuf state, part;   // muted[S], cnt[S]; the tile sums of a call (grows on demand)
+    int configure(int streams, double level_) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = out_dtype = SDRGPU_C64;
+        level = (float)level_;
+        return SDRGPU_OK;
+    }
+    int init() override { return reset(); }
+    int reset() override { return upload(state, std::vector<int>(2 * (size_t)S, 0)); }   // _isMute = false, cnt = 0
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;   // (the reference divides by zero here)
+        const int n = frames * S;
+        SDRGPU_CHECK(part.ensure(sizeof(float) * (size_t)((frames + BANK_F - 1) / BANK_F) * S));
+        hipLaunchKernelGGL(bank_squelch_partial_kernel, tiles_by_waves(frames, S), dim3(BANK_W), 0, s, (const float2*)in, frames, S,
+                           part.as<float>());
+        hipLaunchKernelGGL(bank_squelch_decide_kernel, waves_of(S), dim3(BANK_W), 0, s, part.as<float>(), frames, S, level,
+                           state.as<int>());
+        hipLaunchKernelGGL(bank_squelch_gate_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float2*)in, (float2*)out, n, S,
+                           state.as<int>());
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// ------------------------------------------------------------------- magnitude
+struct BankMag : Bank {
+    int configure(int streams) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = SDRGPU_C64;
+        out_dtype = SDRGPU_F32;
+        return SDRGPU_OK;
+    }
+    int init() override { return SDRGPU_OK; }
+    int reset() override { return SDRGPU_OK; }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int n = frames * S;
+        hipLaunchKernelGGL(bank_magnitude_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float2*)in, (float*)out, n);
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
 // ------------------------------------------------- composites: stages back to back
 // Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers of
 // frames * S elements (sized for C64), which grow on demand.
@@ -415,6 +576,109 @@ extern "C" int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams,
     if (rc >= 0) {
         auto* m = new BankMm();
         rc = c->add(m, m->configure(streams, SDRGPU_F32, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8));
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+// loop::AGC<T> per stream (agc.h:13-147)
+extern "C" int sdrgpu_bank_agc_create(sdrgpu_bank** h, int device, int streams, int dtype, double setPoint, double attack, double decay,
+                                      double maxGain, double maxOutputAmp, double initGain, int enabled) {
+    NEED_BANK_OUT(h, "bank_agc_create");
+    auto* a = new BankAgc();
+    return publish_bank(h, a, device, a->configure(streams, dtype, setPoint, attack, decay, maxGain, maxOutputAmp, initGain, enabled));
+}
+// AGC::setGain (agc.h:31-35) for every stream: of an AGC bank, or of the last AGC of a chain (BankAM's
+// audio AGC, as sdrgpu_demod_agc_set_gain(h, 1, gain))
+extern "C" int sdrgpu_bank_agc_set_gain(sdrgpu_bank* h, float gain) {
+    NEED_BANK(h);
+    auto* a = dynamic_cast<BankAgc*>(h->impl);
+    if (auto* c = dynamic_cast<BankChain*>(h->impl))
+        for (auto& k : c->kids)
+            if (auto* ka = dynamic_cast<BankAgc*>(k.get())) a = ka;
+    if (!a) { set_error("bank_agc_set_gain: the bank has no AGC"); return SDRGPU_ESTATE; }
+    a->set_gain(gain);
+    return SDRGPU_OK;
+}
+// correction::DCBlocker<T> per stream (dc_blocker.h:54-60)
+extern "C" int sdrgpu_bank_dc_blocker_create(sdrgpu_bank** h, int device, int streams, int dtype, double rate) {
+    NEED_BANK_OUT(h, "bank_dc_blocker_create");
+    auto* d = new BankDcb();
+    return publish_bank(h, d, device, d->configure(streams, dtype, rate));
+}
+// filter::Deemphasis<float> per stream (deephasis.h:58-65, 91-94)
+extern "C" int sdrgpu_bank_deemphasis_create(sdrgpu_bank** h, int device, int streams, double tau, double samplerate) {
+    NEED_BANK_OUT(h, "bank_deemphasis_create");
+    auto* d = new BankDeemp();
+    return publish_bank(h, d, device, d->configure(streams, tau, samplerate));
+}
+// noise_reduction::Squelch per stream (squelch.h:33-63)
+extern "C" int sdrgpu_bank_squelch_create(sdrgpu_bank** h, int device, int streams, double level) {
+    NEED_BANK_OUT(h, "bank_squelch_create");
+    auto* q = new BankSquelch();
+    return publish_bank(h, q, device, q->configure(streams, level));
+}
+extern "C" int sdrgpu_bank_squelch_muted(sdrgpu_bank* h, int* muted) {
+    NEED_BANK(h);
+    auto* q = dynamic_cast<BankSquelch*>(h->impl);
+    if (!q || !muted) { set_error("bank_squelch_muted: not a squelch bank, or a null pointer"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(q->device);
+    SDRGPU_HIP(hipDeviceSynchronize());   // (UI-rate query: waits for the bank's queued work)
+    SDRGPU_HIP(hipMemcpy(muted, q->state.p, sizeof(int) * q->S, hipMemcpyDeviceToHost));
+    return SDRGPU_OK;
+}
+
+// a chain of C64 in, F32 out; rc: the status of the checks so far
+static BankChain* new_audio_chain(int streams, int& rc) {
+    auto* c = new BankChain();
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    c->S = std::max(streams, 1);
+    c->in_dtype = SDRGPU_C64;
+    c->out_dtype = SDRGPU_F32;
+    return c;
+}
+
+// demod::FM<float> per stream (fm.h:25-44, 86-93, 117-145): the stages and taps of sdrgpu_fm_create (blocks.hip)
+extern "C" int sdrgpu_bank_fm_create(sdrgpu_bank** h, int device, int streams, double samplerate, double bandwidth, int lowPass,
+                                     int highPass) {
+    NEED_BANK_OUT(h, "bank_fm_create");
+    int rc = SDRGPU_OK;
+    auto* c = new_audio_chain(streams, rc);
+    if (rc >= 0 && (!(samplerate > 0) || !(bandwidth > 0))) { set_error("bank_fm_create: samplerate and bandwidth must be positive"); rc = SDRGPU_EARG; }
+    if (rc >= 0) { auto* q = new BankQuad(); rc = c->add(q, q->configure(streams, hz_to_rads(bandwidth / 2.0, samplerate))); }
+    if (rc >= 0 && (lowPass || highPass)) {
+        std::vector<float> t;
+        rc = (lowPass && highPass) ? design_taps(t, taps_band_pass_f, 300.0, bandwidth / 2.0, 100.0, samplerate, 0)
+             : highPass            ? design_taps(t, taps_high_pass, 300.0, 100.0, samplerate, 0)
+                                   : design_taps(t, taps_low_pass, bandwidth / 2.0, (bandwidth / 2.0) * 0.1, samplerate, 0);
+        if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, f->configure(streams, SDRGPU_F32, t.data(), (int)t.size())); }
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+// demod::AM<float> per stream (am.h:28-49, 114-131): the stages and constants of sdrgpu_am_create (loops.hip), mono
+extern "C" int sdrgpu_bank_am_create(sdrgpu_bank** h, int device, int streams, int agcMode, double bandwidth, double agcAttack,
+                                     double agcDecay, double dcBlockRate, double samplerate) {
+    NEED_BANK_OUT(h, "bank_am_create");
+    int rc = SDRGPU_OK;
+    auto* c = new_audio_chain(streams, rc);
+    if (rc >= 0 && (agcMode < 0 || agcMode > 2 || !(samplerate > 0) || !(bandwidth > 0))) {
+        set_error("bank_am_create: agcMode %d outside 0..2, or samplerate or bandwidth not positive", agcMode);
+        rc = SDRGPU_EARG;
+    }
+    // the AGC of AM (am.h:27-49): set point 1, max gain 10e6, max output 10, initial gain inf
+    auto agc = [&](int dtype, int enabled) {
+        auto* a = new BankAgc();
+        return c->add(a, a->configure(streams, dtype, 1.0, agcAttack, agcDecay, 10e6, 10.0, INFINITY, enabled));
+    };
+    if (rc >= 0 && agcMode == 1) rc = agc(SDRGPU_C64, 1);
+    if (rc >= 0) { auto* m = new BankMag(); rc = c->add(m, m->configure(streams)); }
+    if (rc >= 0) { auto* d = new BankDcb(); rc = c->add(d, d->configure(streams, SDRGPU_F32, dcBlockRate)); }
+    if (rc >= 0 && agcMode != 1) rc = agc(SDRGPU_F32, agcMode == 2);   // audioAgc runs unless CARRIER; enabled only for AUDIO
+    if (rc >= 0) {
+        const double fc = bandwidth / 2.0;
+        std::vector<float> t;
+        rc = design_taps(t, taps_low_pass, fc, fc * 0.1, samplerate, 0);
+        if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, f->configure(streams, SDRGPU_F32, t.data(), (int)t.size())); }
     }
     return publish_bank(h, c, device, rc);
 }

@@ -25,14 +25,11 @@
 // same value. State (average amplitude, gain; DC offset) stays on the device between calls.
 #pragma once
 #include "serial_chunks.h"   // LOOP_CHUNK / LOOP_NT, amp_of / scale_of, serial_chunks
+#include "loop_steps.h"      // AgcParams, agc_step / agc_fixed_step, dcb_step, deemp_step (shared with the banks)
 
 namespace sdrgpu {
 
 // ---------------------------------------------------------------------- AGC
-struct AgcParams {
-    float setPoint, attack, invAttack, decay, invDecay, maxGain, maxOutputAmp;
-    int enabled;
-};
 struct AgcState {
     float amp, gain;
 };
@@ -105,28 +102,9 @@ __global__ __launch_bounds__(LOOP_NT) void agc_kernel(const DT* __restrict__ in,
         }
         if (t == 0) {
             if (p.enabled) {
-                for (int i = 0; i < n; i++) {
-                    const float inAmp = A[i];
-                    if (inAmp != 0.0f) {
-                        amp = (inAmp > amp) ? ((amp * p.invAttack) + (inAmp * p.attack))
-                                            : ((amp * p.invDecay) + (inAmp * p.decay));
-                        const float q = p.setPoint / amp;
-                        gain = (p.maxGain < q) ? p.maxGain : q;              // std::min<float>
-                    } else {
-                        gain = 1.0f;
-                    }
-                    if (inAmp * gain > p.maxOutputAmp) {                     // clip look-ahead
-                        amp = S[i];
-                        const float q = p.setPoint / amp;
-                        gain = (p.maxGain < q) ? p.maxGain : q;
-                    }
-                    G[i] = gain;
-                }
+                for (int i = 0; i < n; i++) G[i] = agc_step(p, A[i], amp, gain, [&] { return S[i]; });
             } else {
-                for (int i = 0; i < n; i++) {
-                    const float inAmp = A[i];
-                    G[i] = (inAmp * gain > p.maxOutputAmp) ? (p.maxOutputAmp / inAmp) : gain;
-                }
+                for (int i = 0; i < n; i++) G[i] = agc_fixed_step(p, A[i], gain);
             }
         }
         __syncthreads();
@@ -196,19 +174,7 @@ __global__ __launch_bounds__(LOOP_NT) void dcb_kernel(const DT* __restrict__ in,
     float2 off = *st;
     serial_chunks(
         count, [&](int i0, int i) { X[i] = in[i0 + i]; },
-        [&](int i) {
-            if constexpr (sizeof(DT) == 4) {
-                const float o = X[i] - off.x;
-                off.x += o * rate;
-                X[i] = o;
-            } else {
-                const float2 v = X[i];
-                const float ox = v.x - off.x, oy = v.y - off.y;
-                off.x += ox * rate;
-                off.y += oy * rate;
-                X[i] = make_float2(ox, oy);
-            }
-        },
+        [&](int i) { X[i] = dcb_step(X[i], off, rate); },
         [&](int i0, int i) { out[i0 + i] = X[i]; });
     if (threadIdx.x == 0) *st = off;
 }
@@ -256,11 +222,7 @@ __global__ __launch_bounds__(LOOP_NT) void deemp_kernel(const float* __restrict_
         count, [&](int i0, int e) { X[e] = in[(size_t)i0 * C + e]; },
         [&](int i) {
 #pragma unroll
-            for (int c = 0; c < C; c++) {
-                const float y = (alpha * X[i * C + c]) + (beta * last[c]);
-                X[i * C + c] = y;
-                last[c] = y;
-            }
+            for (int c = 0; c < C; c++) X[i * C + c] = deemp_step(alpha, beta, X[i * C + c], last[c]);
         },
         [&](int i0, int e) { out[(size_t)i0 * C + e] = X[e]; });
     if (threadIdx.x == 0) *st = make_float2(last[0], last[1]);

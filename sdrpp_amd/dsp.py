@@ -740,6 +740,74 @@ class BankGFSK(Bank):
         super().__init__(h, np.complex64, np.float32)
 
 
+class BankAGC(Bank):
+    """dsp::loop::AGC<T> per stream; arguments as AGC. ``enabled=False`` is the fixed-gain limiter."""
+
+    def __init__(self, streams, set_point, attack, decay, max_gain, max_output_amp, init_gain=1.0, complex_data=False, enabled=True,
+                 device=0):
+        npd = np.complex64 if complex_data else np.float32
+        h = _make(lib.sdrgpu_bank_agc_create, device, int(streams), C64 if complex_data else F32, float(set_point), float(attack),
+                  float(decay), float(max_gain), float(max_output_amp), float(init_gain), int(bool(enabled)))
+        super().__init__(h, npd, npd)
+
+    def set_gain(self, gain):
+        """AGC::setGain for every stream, latched at the next call."""
+        check(lib.sdrgpu_bank_agc_set_gain(self._h, float(gain)))
+
+
+class BankDCBlocker(Bank):
+    """dsp::correction::DCBlocker<T> per stream; rate in 1/sample."""
+
+    def __init__(self, streams, rate, complex_data=False, device=0):
+        npd = np.complex64 if complex_data else np.float32
+        super().__init__(_make(lib.sdrgpu_bank_dc_blocker_create, device, int(streams), C64 if complex_data else F32, float(rate)),
+                         npd, npd)
+
+
+class BankDeemphasis(Bank):
+    """dsp::filter::Deemphasis<float> per stream."""
+
+    def __init__(self, streams, tau, samplerate, device=0):
+        super().__init__(_make(lib.sdrgpu_bank_deemphasis_create, device, int(streams), float(tau), float(samplerate)), np.float32,
+                         np.float32)
+
+
+class BankSquelch(Bank):
+    """dsp::noise_reduction::Squelch per stream; level in dB, the unmute count per stream."""
+
+    def __init__(self, streams, level, device=0):
+        super().__init__(_make(lib.sdrgpu_bank_squelch_create, device, int(streams), float(level)), np.complex64, np.complex64)
+
+    @property
+    def muted(self):
+        """int32[S]: the streams' mute state after the last call (waits for the queued work)."""
+        m = np.empty(self.streams, np.int32)
+        check(lib.sdrgpu_bank_squelch_muted(self._h, m.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return m
+
+
+class BankFM(Bank):
+    """dsp::demod::FM<float> per stream: complex64 -> float32 mono; arguments as FM."""
+
+    def __init__(self, streams, samplerate, bandwidth, low_pass=True, high_pass=False, device=0):
+        h = _make(lib.sdrgpu_bank_fm_create, device, int(streams), float(samplerate), float(bandwidth), int(bool(low_pass)),
+                  int(bool(high_pass)))
+        super().__init__(h, np.complex64, np.float32)
+
+
+class BankAM(Bank):
+    """dsp::demod::AM<float> per stream: complex64 -> float32 mono; agc_mode 0 OFF, 1 CARRIER, 2 AUDIO."""
+
+    def __init__(self, streams, agc_mode, bandwidth, attack, decay, dc_rate, samplerate, device=0):
+        h = _make(lib.sdrgpu_bank_am_create, device, int(streams), int(agc_mode), float(bandwidth), float(attack), float(decay),
+                  float(dc_rate), float(samplerate))
+        super().__init__(h, np.complex64, np.float32)
+
+    def set_agc_gain(self, gain):
+        """setAGCGain: the gain of the chain's AGC for every stream, latched at the next call."""
+        check(lib.sdrgpu_bank_agc_set_gain(self._h, float(gain)))
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
