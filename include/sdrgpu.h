@@ -207,8 +207,14 @@ int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, double bandwidth
 /* demod::SSB<T> (demod/ssb.h:20-105): mode 0 USB, 1 LSB, 2 DSB; stereo != 0 -> stereo_t out */
 int sdrgpu_ssb_create(sdrgpu_block** h, int device, int mode, double bandwidth, double samplerate, int agcEnabled,
                       double agcAttack, double agcDecay, int stereo);
-/* AGC inside an AM / SSB handle: which 0 = first AGC (AM carrier AGC, SSB AGC), 1 = last (AM audio AGC);
- * am.h:63-97 setAGCGain/getAGCGain/setAGCAttack/setAGCDecay, ssb.h:62-84 */
+/* demod::CW<T> (demod/cw.h:15-28, 72-85): xlate by hzToRads(tone, samplerate) -> Re -> AGC(1, attack, decay,
+ * 10e6, 1.0, 1.0), enabled iff agcEnabled [-> MonoToStereo]; arguments in CW::init's order; stereo != 0 ->
+ * stereo_t out. sdrgpu_block_reset resets the phase and the AGC. */
+int sdrgpu_cw_create(sdrgpu_block** h, int device, double tone, int agcEnabled, double agcAttack, double agcDecay,
+                     double samplerate, int stereo);
+int sdrgpu_cw_set_tone(sdrgpu_block* h, double tone);   /* cw.h:30-35: phase kept; SDRGPU_ESTATE on another handle */
+/* AGC inside an AM / SSB / CW handle: which 0 = first AGC (AM carrier AGC, SSB AGC, CW AGC), 1 = last (AM
+ * audio AGC); am.h:63-97 setAGCGain/getAGCGain/setAGCAttack/setAGCDecay, ssb.h:62-84, cw.h:37-63 */
 int sdrgpu_demod_agc_set_gain(sdrgpu_block* h, int which, float gain);
 int sdrgpu_demod_agc_get_gain(sdrgpu_block* h, int which, float* gain);
 int sdrgpu_demod_agc_set_enabled(sdrgpu_block* h, int which, int enabled);
@@ -342,7 +348,8 @@ int sdrgpu_block_destroy(sdrgpu_block* h);
  * `frames` rows; state and history stay on the device, and results do not depend on how the rows are
  * cut into calls. The loops (FastAGC, Costas, MM) run one lane per stream, 64 streams per wave, on the
  * per-sample steps of the single-stream kernels: every column is bit-identical to the single-stream
- * block fed that column. Parameters are fixed at creation (sdrgpu_bank_agc_set_gain excepted).
+ * block fed that column. Parameters are fixed at creation (sdrgpu_bank_agc_set_gain and
+ * sdrgpu_bank_xlator_set_offset excepted).
  * Every create function takes (handle, device, streams, the arguments of the single-stream create
  * function in its order) and applies that function's checks; streams < 1 is SDRGPU_EARG. All checks run
  * before the device is selected. frames * streams beyond INT_MAX (the kernels' index type) is
@@ -393,7 +400,8 @@ int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams, double sym
 int sdrgpu_bank_agc_create(sdrgpu_bank** h, int device, int streams, int dtype, double setPoint, double attack, double decay,
                            double maxGain, double maxOutputAmp, double initGain, int enabled);
 /* AGC::setGain (agc.h:31-35) for all streams, latched at the next call with rows; also on a
- * sdrgpu_bank_am_create handle (the last AGC of the chain: its audio AGC); SDRGPU_ESTATE without an AGC */
+ * sdrgpu_bank_am_create / _ssb_create / _cw_create handle (the last AGC of the chain: AM's audio AGC);
+ * SDRGPU_ESTATE without an AGC */
 int sdrgpu_bank_agc_set_gain(sdrgpu_bank* h, float gain);
 /* correction::DCBlocker<T> per stream (correction/dc_blocker.h:54-60), dtype F32 or C64; offset 0 at create / reset */
 int sdrgpu_bank_dc_blocker_create(sdrgpu_bank** h, int device, int streams, int dtype, double rate);
@@ -417,6 +425,29 @@ int sdrgpu_bank_fm_create(sdrgpu_bank** h, int device, int streams, double sampl
  * 0.1 bandwidth / 2, samplerate)); C64 -> F32 mono; bit-identical to those banks run one after another */
 int sdrgpu_bank_am_create(sdrgpu_bank** h, int device, int streams, int agcMode, double bandwidth, double agcAttack,
                           double agcDecay, double dcBlockRate, double samplerate);
+
+/* -- SSB and CW receiver banks */
+/* channel::FrequencyXlator per stream (channel/frequency_xlator.h:15-50): one offset and one running phase
+ * shared by all streams (they start together): out[m*S + k] = in[m*S + k] * nco(row m), the NCO of
+ * sdrgpu_xlator_create; column k is bit-identical to such a handle fed column k in the same calls. C64 -> C64;
+ * reset zeroes the phase (frequency_xlator.h:35-41) */
+int sdrgpu_bank_xlator_create(sdrgpu_bank** h, int device, int streams, double offsetRad);
+/* the same followed by convert::ComplexToReal (ssb.h:92-93, cw.h:73-75) in one launch: C64 -> F32, bit-identical
+ * to the real part of the xlator bank's output; the first stage of the SSB and CW banks on its own */
+int sdrgpu_bank_xlator_real_create(sdrgpu_bank** h, int device, int streams, double offsetRad);
+/* setOffset (frequency_xlator.h:25-29): keeps the running phase, applies from the next call; also on a
+ * sdrgpu_bank_ssb_create / sdrgpu_bank_cw_create handle (its xlator); SDRGPU_ESTATE without one */
+int sdrgpu_bank_xlator_set_offset(sdrgpu_bank* h, double offsetRad);
+/* demod::SSB<float> per stream (demod/ssb.h:21-35, 90-105, 119-126): mode 0 USB, 1 LSB, 2 DSB; xlate by
+ * hzToRads(+bandwidth/2 | -bandwidth/2 | 0, samplerate) -> Re -> bank AGC<F32>(1, attack, decay, 10e6, 10, inf),
+ * enabled iff agcEnabled; C64 -> F32 mono; bit-identical to the xlator bank, the real part and the AGC bank
+ * run one after another (the first two are one launch) */
+int sdrgpu_bank_ssb_create(sdrgpu_bank** h, int device, int streams, int mode, double bandwidth, double samplerate,
+                           int agcEnabled, double agcAttack, double agcDecay);
+/* demod::CW<float> per stream (demod/cw.h:15-28, 72-85): xlate by hzToRads(tone, samplerate) -> Re -> bank
+ * AGC<F32>(1, attack, decay, 10e6, 1.0, 1.0); arguments in CW::init's order; C64 -> F32 mono */
+int sdrgpu_bank_cw_create(sdrgpu_bank** h, int device, int streams, double tone, int agcEnabled, double agcAttack,
+                          double agcDecay, double samplerate);
 
 /* device buffers of frames * S (in) and sdrgpu_bank_out_rows(frames) * S (out) elements, on `stream` (0:
  * the handle's own); asynchronous except for a bank that ends in MM (above). Returns the rows written. */

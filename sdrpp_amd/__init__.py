@@ -138,6 +138,11 @@ def _load():
         "sdrgpu_dc_blocker_create": (i, [pp, i, i, d]),
         "sdrgpu_am_create": (i, [pp, i, i, d, d, d, d, d, i]),
         "sdrgpu_ssb_create": (i, [pp, i, i, d, d, i, d, d, i]),
+        "sdrgpu_cw_create": (i, [pp, i, d, i, d, d, d, i]),
+        "sdrgpu_cw_set_tone": (i, [vp, d]),
+        "sdrgpu_demod_agc_set_gain": (i, [vp, i, ctypes.c_float]),
+        "sdrgpu_demod_agc_get_gain": (i, [vp, i, ctypes.POINTER(ctypes.c_float)]),
+        "sdrgpu_demod_agc_set_enabled": (i, [vp, i, i]),
         "sdrgpu_fmif_create": (i, [pp, i, i]),
         "sdrgpu_fmif_set_bins": (i, [vp, i]),
         "sdrgpu_fmif_window": (i, [i, fp]),
@@ -180,6 +185,11 @@ def _load():
         "sdrgpu_bank_squelch_muted": (i, [vp, ctypes.POINTER(i)]),
         "sdrgpu_bank_fm_create": (i, [pp, i, i, d, d, i, i]),
         "sdrgpu_bank_am_create": (i, [pp, i, i, i, d, d, d, d, d]),
+        "sdrgpu_bank_xlator_create": (i, [pp, i, i, d]),
+        "sdrgpu_bank_xlator_real_create": (i, [pp, i, i, d]),
+        "sdrgpu_bank_xlator_set_offset": (i, [vp, d]),
+        "sdrgpu_bank_ssb_create": (i, [pp, i, i, i, d, d, i, d, d]),
+        "sdrgpu_bank_cw_create": (i, [pp, i, i, d, i, d, d, d]),
         "sdrgpu_bank_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_bank_process": (i, [vp, vp, i, vp]),
         "sdrgpu_bank_out_rows": (i, [vp, i]),

@@ -5,8 +5,10 @@
 //   BankFastAgc, BankCostas, BankMm   loop::FastAGC<T>, loop::Costas<ORDER>, clock_recovery::MM<T> per stream
 //   BankAgc, BankDcb, BankDeemp      loop::AGC<T>, correction::DCBlocker<T>, filter::Deemphasis<float> per stream
 //   BankSquelch, BankMag     noise_reduction::Squelch per stream; volk_32fc_magnitude_32f over the flat stream
+//   BankXlator               channel::FrequencyXlator per stream on the single-stream NCO; also as translate -> real part
 //   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip),
-//                            demod::FM<float> / demod::AM<float> per stream (those of blocks.hip / loops.hip)
+//                            demod::FM<float> / demod::AM<float> / demod::SSB<float> / demod::CW<float> per stream
+//                            (those of blocks.hip / loops.hip)
 // Top to bottom: the Bank base and its handle, the blocks (each: configure = the argument checks and the
 // parameters, host only; init = device state; reset; run = its launch), the C entry points.
 // A create function checks every argument (configure, of a chain: of all its stages) before it selects
@@ -435,6 +437,51 @@ struct BankMag : Bank {
     }
 };
 
+// ---------------------------------------------------------------------- xlator
+// channel::FrequencyXlator per stream with the single-stream block's NCO (blocks.h): one offset and one
+// running phase for the bank. `real`: the real part only (C64 -> F32), the first stage of BankSSB / BankCW.
+struct BankXlator : Bank {
+    double w = 0.0;
+    bool real = false;
+    Nco* nco = nullptr;
+    ~BankXlator() override { nco_delete(nco); }
+    int configure(int streams, double offsetRad, bool real_) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!std::isfinite(offsetRad)) { set_error("bank_xlator: offset %g not finite", offsetRad); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = SDRGPU_C64;
+        out_dtype = real_ ? SDRGPU_F32 : SDRGPU_C64;
+        real = real_;
+        w = xlator_effective_omega(offsetRad);
+        return SDRGPU_OK;
+    }
+    int init() override {
+        nco = nco_new();
+        return nco_set_w(nco, w);
+    }
+    int reset() override {   // frequency_xlator.h:35-41
+        nco_reset(nco);
+        return SDRGPU_OK;
+    }
+    int set_offset(double offsetRad) {   // frequency_xlator.h:25-29: the phase is kept
+        if (!std::isfinite(offsetRad)) { set_error("bank_xlator: offset %g not finite", offsetRad); return SDRGPU_EARG; }
+        w = xlator_effective_omega(offsetRad);
+        return nco_set_w(nco, w);
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const float2 *phi, *plo;
+        SDRGPU_CHECK(nco_prepare(nco, frames, s, &phi, &plo));
+        const int chunks = (S + BANK_XS - 1) / BANK_XS;
+        const dim3 grid((unsigned)((frames + BANK_XR - 1) / BANK_XR) * chunks);
+        if (real) hipLaunchKernelGGL(bank_xlate_kernel<true>, grid, dim3(BANK_XS), 0, s, (const float2*)in, out, frames, S, chunks, phi, plo);
+        else hipLaunchKernelGGL(bank_xlate_kernel<false>, grid, dim3(BANK_XS), 0, s, (const float2*)in, out, frames, S, chunks, phi, plo);
+        SDRGPU_HIP(hipGetLastError());
+        nco_advance(nco, frames);
+        return frames;
+    }
+};
+
 // ------------------------------------------------- composites: stages back to back
 // Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers of
 // frames * S elements (sized for C64), which grow on demand.
@@ -445,12 +492,14 @@ struct BankChain : Bank {
     int add(Bank* b, int rc) {
         std::unique_ptr<Bank> k(b);
         if (rc < 0) return rc;
-        k->device = device;
         kids.push_back(std::move(k));
         return SDRGPU_OK;
     }
-    int init() override {
-        for (auto& k : kids) SDRGPU_CHECK(k->init());
+    int init() override {   // (add() ran before the create function knew the device: the kids learn it here)
+        for (auto& k : kids) {
+            k->device = device;
+            SDRGPU_CHECK(k->init());
+        }
         return SDRGPU_OK;
     }
     int reset() override {
@@ -681,6 +730,72 @@ extern "C" int sdrgpu_bank_am_create(sdrgpu_bank** h, int device, int streams, i
         if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, f->configure(streams, SDRGPU_F32, t.data(), (int)t.size())); }
     }
     return publish_bank(h, c, device, rc);
+}
+
+// channel::FrequencyXlator per stream (frequency_xlator.h:15-50)
+extern "C" int sdrgpu_bank_xlator_create(sdrgpu_bank** h, int device, int streams, double offsetRad) {
+    NEED_BANK_OUT(h, "bank_xlator_create");
+    auto* x = new BankXlator();
+    return publish_bank(h, x, device, x->configure(streams, offsetRad, false));
+}
+// ... and its real part in the same launch (convert::ComplexToReal after the xlator: ssb.h:92-93, cw.h:73-75), C64 -> F32:
+// the first stage of BankSSB / BankCW on its own
+extern "C" int sdrgpu_bank_xlator_real_create(sdrgpu_bank** h, int device, int streams, double offsetRad) {
+    NEED_BANK_OUT(h, "bank_xlator_real_create");
+    auto* x = new BankXlator();
+    return publish_bank(h, x, device, x->configure(streams, offsetRad, true));
+}
+// FrequencyXlator::setOffset (frequency_xlator.h:25-29) of an xlator bank, or of the xlator of a BankSSB / BankCW chain
+extern "C" int sdrgpu_bank_xlator_set_offset(sdrgpu_bank* h, double offsetRad) {
+    NEED_BANK(h);
+    auto* x = dynamic_cast<BankXlator*>(h->impl);
+    if (auto* c = dynamic_cast<BankChain*>(h->impl))
+        for (auto& k : c->kids)
+            if (!x) x = dynamic_cast<BankXlator*>(k.get());
+    if (!x) { set_error("bank_xlator_set_offset: the bank has no xlator"); return SDRGPU_ESTATE; }
+    if (!std::isfinite(offsetRad)) { set_error("bank_xlator_set_offset: offset %g not finite", offsetRad); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(h->impl->device);   // (the handle's: a chain's xlator runs where the chain does)
+    SDRGPU_HIP(hipDeviceSynchronize());   // (a queued call still reads the fine table that the setter rewrites)
+    return x->set_offset(offsetRad);
+}
+
+// [xlate by offsetRad -> Re] -> bank AGC<F32>(1, attack, decay, 10e6, maxOutputAmp, initGain): the stages of SSB and CW
+static int publish_xlate_agc(sdrgpu_bank** h, int device, int streams, int rc, double offsetRad, int agcEnabled, double attack,
+                             double decay, double maxOutputAmp, double initGain) {
+    auto* c = new_audio_chain(streams, rc);
+    if (rc >= 0) { auto* x = new BankXlator(); rc = c->add(x, x->configure(streams, offsetRad, true)); }
+    if (rc >= 0) {
+        auto* a = new BankAgc();
+        rc = c->add(a, a->configure(streams, SDRGPU_F32, 1.0, attack, decay, 10e6, maxOutputAmp, initGain, agcEnabled));
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+// demod::SSB<float> per stream (ssb.h:21-35, 90-105, 119-126): the stages and constants of sdrgpu_ssb_create (loops.hip), mono
+extern "C" int sdrgpu_bank_ssb_create(sdrgpu_bank** h, int device, int streams, int mode, double bandwidth, double samplerate,
+                                      int agcEnabled, double agcAttack, double agcDecay) {
+    NEED_BANK_OUT(h, "bank_ssb_create");
+    int rc = SDRGPU_OK;
+    if (mode < 0 || mode > 2 || !std::isfinite(bandwidth) || !std::isfinite(samplerate) || !(samplerate > 0)) {
+        set_error("bank_ssb_create: mode %d outside 0..2, bandwidth not finite, or samplerate not finite and positive", mode);
+        rc = SDRGPU_EARG;
+    }
+    const double tr = mode == 0 ? bandwidth / 2.0 : (mode == 1 ? -bandwidth / 2.0 : 0.0);   // getTranslation (ssb.h:119-126)
+    return publish_xlate_agc(h, device, streams, rc, rc >= 0 ? hz_to_rads(tr, samplerate) : 0.0, agcEnabled, agcAttack, agcDecay, 10.0,
+                             INFINITY);
+}
+
+// demod::CW<float> per stream (cw.h:15-28, 72-85): the stages and constants of sdrgpu_cw_create (loops.hip), mono
+extern "C" int sdrgpu_bank_cw_create(sdrgpu_bank** h, int device, int streams, double tone, int agcEnabled, double agcAttack,
+                                     double agcDecay, double samplerate) {
+    NEED_BANK_OUT(h, "bank_cw_create");
+    int rc = SDRGPU_OK;
+    if (!std::isfinite(tone) || !std::isfinite(samplerate) || !(samplerate > 0)) {
+        set_error("bank_cw_create: tone not finite, or samplerate not finite and positive");
+        rc = SDRGPU_EARG;
+    }
+    return publish_xlate_agc(h, device, streams, rc, rc >= 0 ? hz_to_rads(tone, samplerate) : 0.0, agcEnabled, agcAttack, agcDecay, 1.0,
+                             1.0);
 }
 
 extern "C" int sdrgpu_bank_streams(sdrgpu_bank* h) {

@@ -4,6 +4,7 @@
 // Device code of bank.hip: stream banks. A bank is S independent streams in the channelizer's
 // frame-major layout: element m of stream k is x[m * S + k] (chan_kernels.h writes out[m * M + k]).
 //   demod::Quadrature, filter::FIR<D, float>      one thread per (row, stream), coalesced over streams
+//   channel::FrequencyXlator                       one block per (row group, 256-stream chunk): the row's phasor is the block's
 //   loop::FastAGC<T>, loop::Costas<ORDER>,
 //   clock_recovery::MM<T>                          one lane per stream
 //
@@ -23,8 +24,10 @@
 #pragma once
 // quad_value is the expression of the single-stream quadrature, which blocks.hip compiles with the
 // default contraction: the same contraction here gives the same bits (quad_value.h)
+// (and xlate_value, the expression of the single-stream frequency xlator: nco_value.h)
 #pragma clang fp contract(fast)
 #include "quad_value.h"
+#include "nco_value.h"
 #pragma clang fp contract(off)
 #include "symsync_kernels.h"
 
@@ -225,6 +228,48 @@ __global__ void bank_fir_kernel(const DT* __restrict__ in, DT* __restrict__ out,
         }
     }
     out[i] = acc;
+}
+
+// ------------------------------------------------------------------- xlator
+// channel/frequency_xlator.h:43-50 per stream, one NCO for the bank: out[m S + k] = in[m S + k] * nco(m),
+// the phasor of row m being nco_tab(phi, plo, m) of the single-stream NCO's tables for a call of `frames`
+// samples (xlate_value: xlator_kernel's expression, so column k is a single-stream handle fed column k).
+// All S elements of a row share the phasor, so the row is the block's, not the thread's: block b is
+// the 256-stream chunk b % chunks of the BANK_XR-row group b / chunks (one 32-bit scalar division per
+// block, the pair folded into grid.x as bank_tile_of_block), thread t is stream k = 256 chunk + t in every
+// row of the group. The row index is uniform over the block: the two table reads have a uniform address
+// (scalar loads; 16 bytes per wave and row, against 64 x 8 of samples), and the element index is a
+// uniform 64-bit m S plus k: no per-element division by S. A wave's 64 loads and stores of a row are
+// consecutive 8-byte (C64) or 4-byte (REAL out) words; the group's BANK_XR loads are unrolled and in
+// flight together. Traffic per element: 8 B read, 8 B written; REAL keeps the real component (the real
+// part of the same product: 8 B read, 4 B written, in place of 16 + 12 for the xlator and a real-part pass).
+constexpr int BANK_XR = 8;     // rows per block
+constexpr int BANK_XS = 256;   // streams per block (= threads)
+template <bool REAL>
+__global__ __launch_bounds__(BANK_XS) void bank_xlate_kernel(const float2* __restrict__ in, void* __restrict__ outv, int frames, int S,
+                                                             int chunks, const float2* __restrict__ phi,
+                                                             const float2* __restrict__ plo) {
+    const int g = blockIdx.x / chunks;
+    const int k = (blockIdx.x - g * chunks) * BANK_XS + threadIdx.x;
+    if (k >= S) return;
+    const int m0 = g * BANK_XR, n = min(BANK_XR, frames - m0);
+    const float2* src = in + (size_t)m0 * S + k;
+    // Rows past the group's last reread it, so the loads are unconditional; each value is then pinned to its
+    // VGPRs (as xlate_slot does, fir_rows.h), or the compiler sinks every load into its row's branch below and
+    // the group becomes load, wait, store eight times over.
+    float2 x[BANK_XR];
+#pragma unroll
+    for (int r = 0; r < BANK_XR; r++) x[r] = src[(size_t)min(r, n - 1) * S];
+#pragma unroll
+    for (int r = 0; r < BANK_XR; r++) asm volatile("" : "+v"(x[r].x), "+v"(x[r].y));
+#pragma unroll
+    for (int r = 0; r < BANK_XR; r++) {
+        if (r >= n) break;
+        const float2 y = xlate_value(x[r], phi, plo, m0 + r);
+        const size_t o = (size_t)(m0 + r) * S + k;
+        if constexpr (REAL) reinterpret_cast<float*>(outv)[o] = y.x;
+        else reinterpret_cast<float2*>(outv)[o] = y;
+    }
 }
 
 }  // namespace sdrgpu

@@ -19,16 +19,19 @@ int chain_size(Block* chain);
 Block* chain_kid(Block* chain, int i);
 // the first (or last) kid of type T of the chain behind h; null where h is no chain or has none
 template <typename T>
-T* find_kid(sdrgpu_block* h, bool last) {
-    if (!h || !h->impl) return nullptr;
+T* find_kid(Block* chain, bool last) {
     T* found = nullptr;
-    for (int i = 0, n = chain_size(h->impl); i < n; i++) {
-        if (auto* k = dynamic_cast<T*>(chain_kid(h->impl, i))) {
+    for (int i = 0, n = chain ? chain_size(chain) : 0; i < n; i++) {
+        if (auto* k = dynamic_cast<T*>(chain_kid(chain, i))) {
             found = k;
             if (!last) break;
         }
     }
     return found;
+}
+template <typename T>
+T* find_kid(sdrgpu_block* h, bool last) {
+    return h ? find_kid<T>(h->impl, last) : nullptr;
 }
 // Constructors: the block is returned even where *rc < 0 (the caller deletes it).
 Block* make_fir_block(int dev, int dtype, int ttype, const float* taps, int n, int decim, bool stereo, int* rc);
@@ -67,6 +70,21 @@ int publish_block(::sdrgpu_block** h, Block* b, int rc);
 struct Nco;
 int carry_history(int dtype, const Nco* nco, const DevBuf& hist, const void* in, DevBuf& next, int H, int count,
                   hipStream_t s);
+
+// ---- the xlator's NCO for a translator outside blocks.hip (bank.hip) ----------------------------
+// The host Nco of XlatorBlock, as that block drives it: nco_set_w(w = xlator_effective_omega(offsetRad))
+// keeps the running phase; per call of `count` samples nco_prepare (the per-call coarse table on s; *phi
+// and *plo are the tables nco_tab reads), the launch, then nco_advance(count). The device is selected
+// by the caller.
+Nco* nco_new();
+void nco_delete(Nco* n);
+int nco_set_w(Nco* n, double w);
+int nco_prepare(Nco* n, int count, hipStream_t s, const float2** phi, const float2** plo);
+void nco_advance(Nco* n, long long count);
+void nco_reset(Nco* n);
+// FrequencyXlator::setOffset (frequency_xlator.h:25-29) of an xlator block (make_xlator_block): the phase is kept;
+// waits for the device first (a queued call still reads the table it rewrites); SDRGPU_ESTATE on another block
+int xlator_block_set_offset(Block* xlator, double offsetRad);
 
 // ---- an RxVFO inside the spectrum launches ------------------------------------------------------
 struct VfoStage1;   // fir_rows.h

@@ -139,6 +139,19 @@ struct Nco {
     }
 };
 
+// the same Nco for bank.hip's translator (blocks.h)
+Nco* nco_new() { return new Nco(); }
+void nco_delete(Nco* n) { delete n; }
+int nco_set_w(Nco* n, double w) { return n->set_w(w); }
+int nco_prepare(Nco* n, int count, hipStream_t s, const float2** phi, const float2** plo) {
+    SDRGPU_CHECK(n->prepare(count, s));
+    *phi = n->phi.as<float2>();
+    *plo = n->plo.as<float2>();
+    return SDRGPU_OK;
+}
+void nco_advance(Nco* n, long long count) { n->phase.advance(n->w, count); }
+void nco_reset(Nco* n) { n->phase.reset(); }
+
 // The history carry on its own launch (blocks.h): FirBlock's zero-output call, PolyBlock, BroadcastFM's
 // delay line (loops.hip) and the channelizer (channelizer.hip).
 int carry_history(int dtype, const Nco* nco, const DevBuf& hist, const void* in, DevBuf& next, int H, int count,
@@ -886,6 +899,13 @@ Block* make_quad_block(int dev, double deviationRad, int* rc) {
 Block* make_xlator_block(int dev, double offsetRad, int* rc) {
     return make_xlator(dev, xlator_effective_omega(offsetRad), rc).release();
 }
+int xlator_block_set_offset(Block* xlator, double offsetRad) {
+    auto* x = dynamic_cast<XlatorBlock*>(xlator);
+    if (!x) { set_error("not an xlator"); return SDRGPU_ESTATE; }
+    SDRGPU_SET_DEVICE(x->device);
+    SDRGPU_HIP(hipDeviceSynchronize());   // (a queued call still reads the fine table that set_w rewrites)
+    return x->nco.set_w(xlator_effective_omega(offsetRad));
+}
 
 // PowerDecimator<T> (multirate/power_decimator.h): cascade of plan stages. With
 // `xlFirst` the RxVFO's xlator is fused into the first (full-rate) stage.
@@ -1080,9 +1100,7 @@ extern "C" int sdrgpu_xlator_create(sdrgpu_block** h, int device, double offsetR
 }
 extern "C" int sdrgpu_xlator_set_offset(sdrgpu_block* h, double offsetRad) {
     NEED_HANDLE(h);
-    auto* x = dynamic_cast<XlatorBlock*>(h->impl);
-    if (!x) { set_error("not an xlator"); return SDRGPU_ESTATE; }
-    return x->nco.set_w(xlator_effective_omega(offsetRad));
+    return xlator_block_set_offset(h->impl, offsetRad);
 }
 
 extern "C" int sdrgpu_fir_create(sdrgpu_block** h, int device, int dtype, int ttype, const float* taps, int ntaps, int decim) {

@@ -7,16 +7,9 @@
 #include <type_traits>
 #include <utility>
 #include "quad_value.h"   // quad_atan2f, quad_value
+#include "nco_value.h"    // cmulf, NCO_LO_BITS / NCO_LO, nco_tab
 
 namespace sdrgpu {
-
-// The contraction is spelled out: left to -ffp-contract=fast, a*b - c*d becomes fma(a, b, -cd) in one
-// kernel and fma(-c, d, ab) in another (the SLP vectoriser's packed form picks the other product),
-// and the spectrum launches' VFO stage 1 then differed from fir_rows_kernel's in the last bit
-// (r4b: test_spectrum_vfo_fused). With explicit fmaf there is one rounding sequence everywhere.
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-    return make_float2(fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x));
-}
 
 // packed-fp32 pairs (v_pk_fma_f32 and friends: one instruction for both components, each the same IEEE
 // operation as its scalar form)
@@ -46,17 +39,7 @@ __device__ __forceinline__ float2 xlate_slot(float2 x, float2 ph0, float2 step) 
     return r;
 }
 
-// Two-level NCO table: phasor(i) = Phi[i >> 12] * Plo[i & 4095], with
-// Plo[k] = exp(i w k) (fixed per configuration, fp64 -> float on the host) and
-// Phi[j] = exp(i (theta0 + w 4096 j)) (per call, fp64 on the device). Two cached
-// loads + one complex multiply per sample instead of an fp64 argument reduction
-// and a sincos; error <= ~2 ulp of the phasor, no drift (theta0 is carried in
-// double-double on the host).
-constexpr int NCO_LO_BITS = 12;
-constexpr int NCO_LO = 1 << NCO_LO_BITS;
-__device__ __forceinline__ float2 nco_tab(const float2* __restrict__ phi, const float2* __restrict__ plo, long long i) {
-    return cmulf(phi[i >> NCO_LO_BITS], plo[i & (NCO_LO - 1)]);
-}
+// the coarse factor of the two-level NCO table (nco_value.h), fp64 on the device
 __device__ __forceinline__ float2 nco_phi(double theta0, double w, long long j) {
     const double TWO_PI = 6.283185307179586476925286766559;
     double a = fma(w * (double)NCO_LO, (double)j, theta0);

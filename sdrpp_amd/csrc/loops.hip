@@ -3,6 +3,7 @@
 //   loop::AGC<T>, correction::DCBlocker, noise_reduction::NoiseBlanker, filter::Deemphasis<T>
 //   demod::AM<T>        demod/am.h:114-142     ([carrier AGC] -> |x| -> DC block -> [audio AGC] -> LPF)
 //   demod::SSB<T>       demod/ssb.h:90-105     (xlate +-bw/2 -> Re -> AGC)
+//   demod::CW<T>        demod/cw.h:72-85       (xlate tone -> Re -> AGC)
 //   demod::BroadcastFM  demod/broadcast_fm.h   (stereo decoder and RDS branch)
 // Top to bottom: the block structs (each: configuration, state, setup / reset, its launch in run),
 // the chain-building helpers, the C entry points. Handles are published through publish_block
@@ -354,17 +355,46 @@ static int append_map(Block* chain, int dev, MapKind kind) {
     return chain_append(chain, m);
 }
 // the AGC of AM (am.h:27-49) and SSB (ssb.h:27-40): set point 1, max gain 10e6, max output 10, initial
-// gain inf; `enabled` false = the fixed-gain limiter (setAGCGain path)
-static AgcBlock* make_demod_agc(int dev, int dtype, double attack, double decay, bool enabled, int* rc) {
+// gain inf; of CW (cw.h:20): max output 1, initial gain 1; `enabled` false = the fixed-gain limiter
+// (setAGCGain path)
+static AgcBlock* make_demod_agc(int dev, int dtype, double attack, double decay, bool enabled, int* rc,
+                                double maxOutputAmp = 10.0, double initGain = INFINITY) {
     auto* a = new AgcBlock();
-    *rc = a->setup(dev, dtype, 1.0, attack, decay, 10e6, 10.0, INFINITY);
+    *rc = a->setup(dev, dtype, 1.0, attack, decay, 10e6, maxOutputAmp, initGain);
     a->p.enabled = enabled ? 1 : 0;
     return a;
 }
-// AGC access inside the AM / SSB chains: `which` 0 = the first AGC of the chain (AM carrier
-// AGC in CARRIER mode, the SSB AGC), 1 = the last (AM audio AGC)
+// xlate -> Re -> AGC [-> MonoToStereo] (ssb.h:90-105, cw.h:72-85) into the new chain *c; *xl: its xlator
+static int xlate_agc_chain(int device, double offsetRad, bool agcEnabled, double attack, double decay, double maxOutputAmp,
+                           double initGain, bool stereo, Block** c, Block** xl = nullptr) {
+    int rc = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32, c);
+    if (rc < 0) return rc;
+    Block* x = make_xlator_block(device, offsetRad, &rc);
+    if (xl) *xl = x;
+    rc = append_owned(*c, x, rc);
+    if (rc >= 0) rc = append_map(*c, device, MapKind::RealPart);
+    if (rc >= 0) {
+        Block* a = make_demod_agc(device, SDRGPU_F32, attack, decay, agcEnabled, &rc, maxOutputAmp, initGain);
+        rc = append_owned(*c, a, rc);
+    }
+    if (rc >= 0 && stereo) rc = append_map(*c, device, MapKind::MonoToStereo);
+    return rc;
+}
+// demod::CW<T> (cw.h): the chain above behind a block of its own, which knows the sample rate of setTone
+struct CwBlock : Block {
+    std::unique_ptr<Block> chain;
+    Block* xlator = nullptr;   // (the chain's)
+    double samplerate = 1.0;
+    int out_count(int count) override { return chain->out_count(count); }
+    int reset() override { return chain->reset(); }
+    int run(const void* in, int count, void* out, hipStream_t s) override { return chain->run(in, count, out, s); }
+};
+// AGC access inside the AM / SSB / CW chains: `which` 0 = the first AGC of the chain (AM carrier
+// AGC in CARRIER mode, the SSB and CW AGC), 1 = the last (AM audio AGC)
 static AgcBlock* demod_agc(sdrgpu_block* h, int which) {
-    AgcBlock* a = find_kid<AgcBlock>(h, which != 0);
+    Block* chain = h ? h->impl : nullptr;
+    if (auto* cw = dynamic_cast<CwBlock*>(chain)) chain = cw->chain.get();
+    AgcBlock* a = find_kid<AgcBlock>(chain, which != 0);
     if (!a) set_error("demod has no AGC");
     return a;
 }
@@ -480,18 +510,34 @@ extern "C" int sdrgpu_ssb_create(sdrgpu_block** h, int device, int mode, double 
                                  int agcEnabled, double agcAttack, double agcDecay, int stereo) {
     if (!h || mode < 0 || mode > 2) { set_error("ssb_create: bad argument"); return SDRGPU_EARG; }
     Block* c = nullptr;
-    int rc = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32, &c);
-    if (rc < 0) return rc;
     const double tr = mode == 0 ? bandwidth / 2.0 : (mode == 1 ? -bandwidth / 2.0 : 0.0);   // getTranslation
-    Block* x = make_xlator_block(device, hz_to_rads(tr, samplerate), &rc);
-    rc = append_owned(c, x, rc);
-    if (rc >= 0) rc = append_map(c, device, MapKind::RealPart);
-    if (rc >= 0) {
-        Block* a = make_demod_agc(device, SDRGPU_F32, agcAttack, agcDecay, agcEnabled != 0, &rc);
-        rc = append_owned(c, a, rc);
-    }
-    if (rc >= 0 && stereo) rc = append_map(c, device, MapKind::MonoToStereo);
+    const int rc = xlate_agc_chain(device, hz_to_rads(tr, samplerate), agcEnabled != 0, agcAttack, agcDecay, 10.0, INFINITY, stereo != 0, &c);
     return publish_block(h, c, rc);
+}
+
+// demod::CW<T> (cw.h:15-28, 72-85): the SSB chain with the tone as translation and the AGC's max output and
+// initial gain at 1 (cw.h:20)
+extern "C" int sdrgpu_cw_create(sdrgpu_block** h, int device, double tone, int agcEnabled, double agcAttack, double agcDecay,
+                                double samplerate, int stereo) {
+    if (!h || !std::isfinite(tone) || !std::isfinite(samplerate) || !(samplerate > 0)) { set_error("cw_create: bad argument"); return SDRGPU_EARG; }
+    auto* w = new CwBlock();
+    w->device = device;
+    w->in_dtype = SDRGPU_C64;
+    w->out_dtype = stereo ? SDRGPU_C64 : SDRGPU_F32;
+    w->samplerate = samplerate;
+    Block* c = nullptr;
+    int rc = xlate_agc_chain(device, hz_to_rads(tone, samplerate), agcEnabled != 0, agcAttack, agcDecay, 1.0, 1.0, stereo != 0, &c, &w->xlator);
+    w->chain.reset(c);
+    if (rc >= 0) rc = w->init_stream();
+    return publish_block(h, w, rc);
+}
+// CW::setTone (cw.h:30-35): the xlator's offset changes, its phase is kept
+extern "C" int sdrgpu_cw_set_tone(sdrgpu_block* h, double tone) {
+    if (!h || !h->impl) { set_error("null block handle"); return SDRGPU_EARG; }
+    auto* w = dynamic_cast<CwBlock*>(h->impl);
+    if (!w) { set_error("not a CW block"); return SDRGPU_ESTATE; }
+    if (!std::isfinite(tone)) { set_error("cw_set_tone: tone not finite"); return SDRGPU_EARG; }
+    return xlator_block_set_offset(w->xlator, hz_to_rads(tone, w->samplerate));
 }
 
 extern "C" int sdrgpu_demod_agc_set_gain(sdrgpu_block* h, int which, float gain) {

@@ -808,6 +808,49 @@ class BankAM(Bank):
         check(lib.sdrgpu_bank_agc_set_gain(self._h, float(gain)))
 
 
+class BankXlator(Bank):
+    """dsp::channel::FrequencyXlator per stream: one offset (rad/sample) and one running phase for the bank.
+    ``real=True`` keeps the real part only (complex64 -> float32, one launch): the first stage of BankSSB / BankCW."""
+
+    def __init__(self, streams, offset_rad, real=False, device=0):
+        fn = lib.sdrgpu_bank_xlator_real_create if real else lib.sdrgpu_bank_xlator_create
+        super().__init__(_make(fn, device, int(streams), float(offset_rad)), np.complex64, np.float32 if real else np.complex64)
+
+    def set_offset(self, offset_rad):
+        """setOffset: the phase is kept, the offset applies from the next call."""
+        check(lib.sdrgpu_bank_xlator_set_offset(self._h, float(offset_rad)))
+
+
+class _XlateAgcBank(Bank):
+    """translate -> real part -> AGC per stream: complex64 -> float32 mono (BankSSB, BankCW)."""
+
+    def set_offset(self, offset_rad):
+        """setOffset of the chain's xlator (rad/sample): the phase is kept."""
+        check(lib.sdrgpu_bank_xlator_set_offset(self._h, float(offset_rad)))
+
+    def set_agc_gain(self, gain):
+        """setAGCGain: the gain of the chain's AGC for every stream, latched at the next call."""
+        check(lib.sdrgpu_bank_agc_set_gain(self._h, float(gain)))
+
+
+class BankSSB(_XlateAgcBank):
+    """dsp::demod::SSB<float> per stream; mode 0 USB, 1 LSB, 2 DSB; arguments as SSB."""
+
+    def __init__(self, streams, mode, bandwidth, samplerate, agc_enabled, attack, decay, device=0):
+        h = _make(lib.sdrgpu_bank_ssb_create, device, int(streams), int(mode), float(bandwidth), float(samplerate),
+                  int(bool(agc_enabled)), float(attack), float(decay))
+        super().__init__(h, np.complex64, np.float32)
+
+
+class BankCW(_XlateAgcBank):
+    """dsp::demod::CW<float> per stream; arguments as CW."""
+
+    def __init__(self, streams, tone, agc_enabled, attack, decay, samplerate, device=0):
+        h = _make(lib.sdrgpu_bank_cw_create, device, int(streams), float(tone), int(bool(agc_enabled)), float(attack),
+                  float(decay), float(samplerate))
+        super().__init__(h, np.complex64, np.float32)
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
@@ -833,6 +876,19 @@ class SSB(Block):
         h = _make(lib.sdrgpu_ssb_create, device, int(mode), float(bandwidth), float(samplerate), int(bool(agc_enabled)),
                   float(attack), float(decay), int(bool(stereo)))
         super().__init__(h, np.complex64, STEREO if stereo else np.float32)
+
+
+class CW(Block):
+    """dsp::demod::CW<T> (demod/cw.h); arguments in CW::init's order."""
+
+    def __init__(self, tone, agc_enabled, attack, decay, samplerate, stereo=False, device=0):
+        h = _make(lib.sdrgpu_cw_create, device, float(tone), int(bool(agc_enabled)), float(attack), float(decay),
+                  float(samplerate), int(bool(stereo)))
+        super().__init__(h, np.complex64, STEREO if stereo else np.float32)
+
+    def set_tone(self, tone):
+        """setTone: the xlator's phase is kept."""
+        check(lib.sdrgpu_cw_set_tone(self._h, float(tone)))
 
 
 class IQFrontEnd:
