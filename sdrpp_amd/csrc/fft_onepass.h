@@ -18,7 +18,8 @@ namespace sdrgpu {
 // A frame's two workgroups (quarters 0-1 and 2-3, the pair's bins 4 m + r0, 4 m + r0 + 1 adjacent so
 // the dB rows leave as 8-byte pairs) sit on one XCD (blocks of 8 frames under round-robin dispatch, for
 // speed only), so the frame is fetched from HBM once per reader and its second read is mostly served by
-// that XCD's L2. The rows stream into LDS by LDS-DMA through a ring of row sets (below). The default
+// that XCD's L2. The rows stream into LDS by LDS-DMA through a wave-private ring of row sets (below: every wave
+// fetches what its own threads read, so the row loop has no barrier; round 15, profiles/r15/README.md). The default
 // since round 5 (C5 group 1.51 ms, 20.9 B/sample of fabric traffic, against 1.63 ms and 30.4 B for the
 // two-pass launches). Rejected forms: one item per
 // workgroup (1.89 ms), a persistent software-pipelined quarter-per-workgroup walk (2.06 ms, spills), the
@@ -82,13 +83,18 @@ constexpr int k1pSlots = 5;   // LDS-DMA ring slots (24 KiB row sets) in the ima
 constexpr int k1pPB = 2;   // (PAD) sample rows per load batch: 4 PB loads of x and of w, two batches in flight
 #ifndef SDRGPU_1P_ABL
 #define SDRGPU_1P_ABL 0   // (ablation builds, wrong results, timing only) 1: no loads, 2: no transforms, 4: no VFO,
-                          // 8: fp32 stage-1 twiddles, 16: no dB / stores
+                          // 8: fp32 stage-1 twiddles, 16: no dB / stores (32, round 15 only: the shared row ring without
+                          // its 32 barriers, group 1.449 -> 1.383 ms, the ceiling of the wave-private ring; profiles/r15)
 #endif
 // Decided A/Bs, kept forms only: the ring's first k1pSlots - 1 row sets are issued before the VFO half, so they
 // land while it computes (C5 group 1.518 -> 1.499 ms, same bits, r6g); quarter r0 + 1's W_128 products run
-// during quarter r0's stage-3 reads (C5 group 1.4748 / 1.4833 vs 1.4782 / 1.4880 ms, r7t, r7u, same bits).
+// during quarter r0's stage-3 reads (C5 group 1.4748 / 1.4833 vs 1.4782 / 1.4880 ms, r7t, r7u, same bits); every
+// wave DMAs the bytes its own threads read, so the ring loop has no barrier, and holds its lanes' offsets over the
+// loop (C5 group 1.451 -> 1.419 ms, same bits; recomputed per row set 1.427-1.439 ms; r15c, r15d). Measured and not
+// kept (profiles/r15): stage 2 without the barrier between its reads and writes, which orders nothing across waves
+// (1.435 vs 1.448 and 1.435 vs 1.421 ms alone, 1.409 vs 1.419 ms beside the ring: inside the run-to-run spread).
 #ifdef SDRGPU_1P_TIMING   // (measurement builds) per-item phase stamps of wave 0: slots 0-7 and 9 (the first
-                          // ring barrier) s_memtime; slot 8 the CU's identity, XCC_ID << 32 | HW_ID
+                          // ring wait) s_memtime; slot 8 the CU's identity, XCC_ID << 32 | HW_ID
 constexpr int k1pStamps = 10;
 __device__ unsigned long long g_1p_t[16384 * k1pStamps];
 #define T1P_AT(item, k)                                                                               \
@@ -169,6 +175,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
         lds[TW512 + t] = ka.tab[t];
         if (t < 64) reinterpret_cast<double2*>(reinterpret_cast<char*>(lds) + op1::W128D)[t] = ka.tab64[2048 + 32 * (2 * p + (t >> 5)) + (t & 31)];
     }
+    __syncthreads();   // (the tables staged: an item's W_128 products read them in front of its first barrier)
     const unsigned lim = PAD ? (unsigned)ka.nz : 65536u;     // (PAD: range-checked loads, 0 past nz)
     const __amdgpu_buffer_rsrc_t rw = brsrc(ka.win, lim * 4u);
     // Whole frames: the rows stream into LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave
@@ -176,51 +183,57 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
     // unused) image region. A row set = row i of the four quarters: x 4 x 4 KiB, w 4 x 2 KiB = 24
     // wave instructions, 3 per wave. 8- and 4-byte register loads reached ~25 GB/s per CU here
     // (the r5 phase stamps: the load phase was 60% of a workgroup's life); 16-B accesses are the
-    // L2 path's full rate. Each wave waits for its own pieces of row set i (counted vmcnt: the
-    // younger row sets stay in flight), a raw s_barrier makes every wave's pieces visible and
-    // frees slot i - 1, the wave issues row set i + k1pSlots - 1 into that slot, then every thread
-    // reads its sample t of the four quarters (ds_read_b64 / _b32, conflict-free) and combines.
-    constexpr int S = k1pSlots, SLOT = 24576;
+    // L2 path's full rate. The ring is wave-private: a DMA's LDS destination is wave-uniform but its
+    // source address is per lane, so wave v fetches exactly the samples 64 v .. 64 v + 63 of row i that
+    // its own threads read, into its own 3-KiB region of the slot: x of quarter j at 512 j (two
+    // instructions: lanes 0-31 quarter 2 e, lanes 32-63 quarter 2 e + 1, 16 B = 2 samples per lane), w of
+    // quarter j at 2048 + 256 j (one instruction: lanes 16 j .. 16 j + 15, 16 B = 4 values per lane).
+    // Nothing a wave reads was fetched by another wave, so the loop has no barrier (it had one per row
+    // set, where all eight waves waited for the slowest of 24 DMAs): the wave waits for its own pieces
+    // of row set i (counted vmcnt: the younger row sets stay in flight), issues row set i + k1pSlots - 1
+    // into its region of slot i - 1, then every thread reads its sample of the four quarters (ds_read_b64
+    // at 8 lane, _b32 at 4 lane of a region: consecutive addresses, conflict-free) and combines.
+    constexpr int S = k1pSlots, SLOT = 24576, WREG = SLOT / 8;
     typedef __attribute__((address_space(3))) char lchar;
     lchar* const lds3 = (lchar*)lds;
     unsigned ldsBase = (unsigned)(size_t)lds3;
     int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // this wave's 3 pieces of every row set (wave-uniform): byte offset of row 0 in the frame (x pieces:
-    // 128 samples of one quarter, 16 B = 2 samples per lane) or in the window (w pieces: 256 values, 16 B
-    // = 4 per lane), row step, offset in the slot; gb: an item's row pointers (set_rows)
+    // gb: the wave's 3 row pointers of an item (x of quarters 0-1, of quarters 2-3, w), at its 64 samples of row 0
+    // (the geometry is scalar arithmetic on the laundered wave index where it is used)
     const char* gb[3];
-    unsigned goff[3], rstep[3], loff[3];
-#pragma unroll
-    for (int e = 0; e < 3; e++) {
-        const int m = 3 * wave + e;
-        const int jx = m >> 2, cx = m & 3, jw = (m - 16) >> 1, cw = (m - 16) & 1;
-        goff[e] = m < 16 ? (unsigned)(M * jx + 128 * cx) * 8u : (unsigned)(M * jw + 256 * cw) * 4u;
-        rstep[e] = m < 16 ? 512u * 8u : 512u * 4u;
-        loff[e] = m < 16 ? (unsigned)(4096 * jx + 1024 * cx) : (unsigned)(16384 + 2048 * jw + 1024 * cw);
-    }
     auto set_rows = [&](const float2* xf, const float* w) {   // (the frame base is all of the ring that depends on the item)
-#pragma unroll
-        for (int e = 0; e < 3; e++)
-            gb[e] = (3 * wave + e < 16 ? reinterpret_cast<const char*>(xf) : reinterpret_cast<const char*>(w)) + goff[e];
+        gb[0] = reinterpret_cast<const char*>(xf + 64 * wave);
+        gb[1] = reinterpret_cast<const char*>(xf + 2 * M + 64 * wave);
+        gb[2] = reinterpret_cast<const char*>(w + 64 * wave);
+    };
+    // a lane's byte offsets in a piece: x, two 512-B runs a quarter apart; w, four 256-B runs a quarter apart
+    auto lane_offs = [&](unsigned& xo, unsigned& wo) {
+        const unsigned lane = (unsigned)(tid() & 63);
+        xo = (lane >> 5) * (unsigned)(M * 8) + (lane & 31u) * 16u;
+        wo = (lane >> 4) * (unsigned)(M * 4) + (lane & 15u) * 16u;
     };
     // LDS-DMA in inline asm: the compiler neither counts it (the waits below are explicit) nor
     // drains it with a vmcnt(0) before every LDS read it cannot prove disjoint (it did with the
     // builtin: no row set stayed in flight); M0 set and restored in the same statement
     // (the row pointers advance by one row step per row set, laundered: left alone, the compiler
     // precomputes all 96 pointers and spills them to VGPR lanes)
-    auto dma = [&](auto ic) {
+    auto dma_at = [&](auto ic, unsigned xo, unsigned wo) {
         constexpr int i = decltype(ic)::value;
-        const unsigned lane16 = (unsigned)(tid() & 63) * 16u;
 #pragma unroll
         for (int e = 0; e < 3; e++) {
-            const char* src = gb[e] + lane16;
-            gb[e] += rstep[e];
+            const char* src = gb[e] + (e < 2 ? xo : wo);
+            gb[e] += e < 2 ? 512 * 8 : 512 * 4;
             asm volatile("" : "+s"(gb[e]));
-            const unsigned dst = __builtin_amdgcn_readfirstlane(ldsBase + (unsigned)((i % S) * SLOT) + loff[e]);
+            const unsigned dst = __builtin_amdgcn_readfirstlane(ldsBase + (unsigned)((i % S) * SLOT + 1024 * e) + (unsigned)(WREG * wave));
             unsigned keep;
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                          : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
         }
+    };
+    auto dma = [&](auto ic) {   // (outside the ring loop: the lane's offsets from the laundered thread index, where they are used)
+        unsigned xo, wo;
+        lane_offs(xo, wo);
+        dma_at(ic, xo, wo);
     };
     // Cross-item prefetch: once an item's last image reads are done (stage 3 of quarter r0 + 1, behind a
     // barrier of their own), the next item's first S - 1 row sets are issued into the ring, so they fly
@@ -234,8 +247,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
         asm volatile("" : "+s"(b), "+s"(p));
         if constexpr (kDma) {
             asm volatile("" : "+s"(ldsBase), "+s"(wave));
-#pragma unroll
-            for (int e = 0; e < 3; e++) asm volatile("" : "+s"(goff[e]), "+s"(rstep[e]), "+s"(loff[e]));
         }
         typedef const __attribute__((address_space(4))) char kchar;
         kchar* kp = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -334,21 +345,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
             // store burst ago (and the VFO half's own waits have already drained them), so nothing is left to
             // wait for; from here on only row sets S - 1 .. are in flight, in issue order, as the counts assume.
             if (pre) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // The lane's DMA offsets and its read offsets in a slot stay in four VGPRs over the loop (from the
+            // laundered thread index, per item; recomputed per row set they cost 13 VALU of a 72-instruction step)
+            unsigned xo, wo;
+            lane_offs(xo, wo);
+            const unsigned tl = (unsigned)tid();
+            const unsigned rdx = WREG * (tl >> 6) + 8 * (tl & 63), rdw = WREG * (tl >> 6) + 2048 + 4 * (tl & 63);
             static_for<0, 32>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int younger = (S - 2 < 31 - i) ? S - 2 : 31 - i;   // row sets issued after i, in flight
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * younger) : "memory");   // this wave's pieces of row set i
-                __builtin_amdgcn_s_barrier();   // every wave's pieces landed; every read of slot i - 1 done
-                asm volatile("" ::: "memory");
+                // This wave's pieces of row set i have landed: only its own vmcnt orders its reads behind its DMAs,
+                // and no other wave reads them, so there is no barrier. Its region of slot i - 1 is free for row set
+                // i + S - 1: its reads of it returned before the previous step's combine2 used them, which ran in
+                // front of that step's sched_barrier, in front of this DMA (the lgkmcnt(0) states it, and costs
+                // nothing: the count is already zero).
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(3 * younger) : "memory");
                 if constexpr (i == 0) T1P(9);
-                if constexpr (i + S - 1 < 32) dma(std::integral_constant<int, i + S - 1>{});
-                const int t = tid();
+                if constexpr (i + S - 1 < 32) dma_at(std::integral_constant<int, i + S - 1>{}, xo, wo);
                 const char* slot = reinterpret_cast<const char*>(lds) + (i % S) * SLOT;
                 float2 u[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    const float2 xx = *reinterpret_cast<const float2*>(slot + 4096 * j + 8 * t);
-                    const float ww = *reinterpret_cast<const float*>(slot + 16384 + 2048 * j + 4 * t);
+                    const float2 xx = *reinterpret_cast<const float2*>(slot + rdx + 512 * j);
+                    const float ww = *reinterpret_cast<const float*>(slot + rdw + 256 * j);
                     u[j] = wmul(xx, ww);
                 }
                 combine2(u, za[i], zb[i]);
@@ -384,7 +403,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
         auto transform = [&](auto hc, float2 (&z)[32]) {
             constexpr int h = decltype(hc)::value;
             const int r = r0 + h;
-            __syncthreads();   // (h = 0: the tables staged; h = 1: quarter r0's stage-3 reads of the image are done)
             {   // stage-1 finish: W_128^(r i), radix 32, W_N^(t (4 k2 + r)), into the LDS image
                 const int t = tid();
                 // W_128^(r i) = W_N^(512 r i) as an fp64 product of the fp64 twiddle, rounded once. As an fp32
@@ -400,6 +418,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
                 double2 ce = tab64[t * r], co = zmul(ce, st);
                 const double2 st2 = zmul(st, st);
                 float2* row = lds + pad16(t);
+                // In front of the first image write: every wave's reads of its ring regions (h = 0; they lie under the
+                // image) or of quarter r0's image (h = 1, stage 3) are done. The W_128 products and the radix 32
+                // above touch registers and the tables only, so a wave that is early runs them meanwhile.
+                __syncthreads();
                 if constexpr (SDRGPU_1P_ABL & 8) {
                     const float2 cf = make_float2((float)ce.x, (float)ce.y), sf = make_float2((float)st.x, (float)st.y);
 #pragma unroll
