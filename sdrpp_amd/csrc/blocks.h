@@ -1,14 +1,14 @@
 // What the other translation units call in blocks.hip (host side only): chains of blocks and the
-// block constructors (loops.hip, symsync.hip), the publication of a new handle and the history carry (loops.hip,
-// channelizer.hip, ifnr.hip, symsync.hip), and the hooks through which a spectrum launch carries an RxVFO's stages
-// (fft.hip, frontend.hip).
+// block constructors (loops.hip, symsync.hip), the gate and the publication of a handle (with the rules of who
+// selects the device, owns a stream and waits) and the history carry (loops.hip, channelizer.hip, ifnr.hip,
+// symsync.hip), and the hooks through which a spectrum launch carries an RxVFO's stages (fft.hip, frontend.hip).
 #pragma once
 #include "sdrgpu_internal.h"
 
 namespace sdrgpu {
 
 // ---- composition: a chain of blocks run back to back on one stream ------------------------------
-int chain_new(int dev, int in_dtype, int out_dtype, Block** out);
+Block* chain_new(int dev, int in_dtype, int out_dtype);
 int chain_append(Block* chain, Block* kid);   // takes the kid (deleted on error)
 // a freshly built block (its construction's status in rc) joins the chain, or is deleted
 inline int append_owned(Block* chain, Block* b, int rc) {
@@ -52,16 +52,25 @@ int design_taps(std::vector<float>& t, Fn design, A... args) {
     return SDRGPU_OK;
 }
 
-// ---- publication and ordering --------------------------------------------------------------------
-// Every create function ends in publish_block: rc < 0 deletes b and passes rc on; else the device is
-// synchronised and *h becomes the new handle.
-// The ordering rule, stated once: a block's calls run on non-blocking streams, which the null stream
-// does not order, so a C entry point that wrote device state on the null stream (a memset or a copy
-// in setup(), reset() or a setter) ends with hipDeviceSynchronize(). That is publish_block for a
-// create, sdrgpu_block_reset for a reset, and the setter itself otherwise (sdrgpu_fmif_set_bins;
-// sdrgpu_broadcast_fm_set_rds when it builds the RDS chain). Block::reset() implementations do not
-// synchronise: a chain's reset pays for one, not one per kid. (A setter whose only device write is a
-// blocking hipMemcpy from host memory, AgcBlock::set_gain, has nothing pending when it returns.)
+// ---- entry points: device, stream, ordering ------------------------------------------------------
+// The entry rule, stated once: for a block handle, only the C entry points (and enter_block / publish_block,
+// which they call for this purpose) select the device, create the handle's stream and wait for the device.
+// Block members (run, reset, setters, the setup of a kid) assume the handle's device is current and touch no
+// stream but the one they are given: a chain's kids, inner chains and BroadcastFM's RDS branch have none.
+// enter_block is the gate of an extern "C" function that takes a sdrgpu_block* and touches the device: a null
+// handle is SDRGPU_EARG, else the handle's device is selected and, with `wait`, idle on return. A create
+// function selects the device once its own argument checks are done and ends in publish_block: rc < 0 deletes
+// b and passes rc on; else b gets the handle's one stream, the device is synchronised and *h is the new handle.
+// The ordering rule, stated once: a block's calls run on non-blocking streams, which the null stream does not
+// order. An entry point that rewrites device state which a queued call may still read or write (a reset, an
+// NCO or tap table, a latched gain; a query that reads state back) waits first: enter_block(h, true). One that
+// wrote device state on the null stream (a memset or a copy in setup(), reset() or a setter) ends with
+// hipDeviceSynchronize(): publish_block for a create, sdrgpu_block_reset for a reset, and the setter itself
+// otherwise (sdrgpu_fmif_set_bins; sdrgpu_broadcast_fm_set_rds when it builds the RDS chain). Block::reset()
+// implementations do not synchronise: a chain's reset pays for one, not one per kid. (A setter whose only device
+// write is a blocking hipMemcpy from host memory, AgcBlock::set_gain, has nothing pending when it returns; one
+// that only latches host-side parameters, the next call's kernel arguments, needs neither wait.)
+int enter_block(::sdrgpu_block* h, bool wait = false);
 int publish_block(::sdrgpu_block** h, Block* b, int rc);
 
 // The history carry on its own launch (fir_hist_kernel): next = the last H elements (of dtype) of
@@ -83,7 +92,7 @@ int nco_prepare(Nco* n, int count, hipStream_t s, const float2** phi, const floa
 void nco_advance(Nco* n, long long count);
 void nco_reset(Nco* n);
 // FrequencyXlator::setOffset (frequency_xlator.h:25-29) of an xlator block (make_xlator_block): the phase is kept;
-// waits for the device first (a queued call still reads the table it rewrites); SDRGPU_ESTATE on another block
+// SDRGPU_ESTATE on another block. The caller has waited for the device: a queued call still reads the table.
 int xlator_block_set_offset(Block* xlator, double offsetRad);
 
 // ---- an RxVFO inside the spectrum launches ------------------------------------------------------
@@ -95,6 +104,7 @@ struct TailArgs;    // fir_tail.h
 // 0: not -- the caller then runs the VFO on its own; < 0: error); the caller launches all M / (16 *
 // RS) segment workgroups (16 segments of 128 outputs each) and the history workgroup; then
 // vfo_stage1_finish commits the stage's state and runs the VFO's remaining stages into `out`.
+// These hooks are block members in effect: the caller's entry point has selected the device.
 int vfo_stage1_prepare(::sdrgpu_block* vfo, const void* in, int count, VfoStage1* st);
 int vfo_stage1_finish(::sdrgpu_block* vfo, const VfoStage1& st, void* out, hipStream_t s);
 // the tail of a VFO whose first stage ran in the front end's pass-A launch, as the pass-B launch

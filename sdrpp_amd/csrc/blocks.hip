@@ -13,7 +13,10 @@
 //      (make_fir, make_xlator, make_quad_block, new_chain), PowerDecimator / RationalResampler
 //      composition, VfoBlock, WfmBlock;
 //   6. the hooks of a VFO carried by the spectrum launches (vfo_stage1_* / vfo_tail_*);
-//   7. the C ABI: create functions (one publish_block() each), process / reset / destroy, converters.
+//   7. enter_block and publish_block, then the C ABI: create functions (one publish_block() each), setters,
+//      process / reset / destroy, converters.
+// Only section 7 selects the device, creates a stream (publish_block: one per handle) or waits for the
+// device; the block structs and the hooks above assume the handle's device is current (blocks.h).
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -89,11 +92,6 @@ StreamOrder::~StreamOrder() {
 
 Block::~Block() {
     if (own) (void)hipStreamDestroy(own);
-}
-int Block::init_stream() {
-    SDRGPU_SET_DEVICE(device);
-    SDRGPU_HIP(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
-    return SDRGPU_OK;
 }
 
 // host side of the NCO tables
@@ -213,22 +211,24 @@ struct FirBlock : Block {
         if (const char* e = tuning_env("SDRGPU_FIR_ROWS")) useRows = atoi(e);
     }
 
+    static int decim_ok(int d) {
+        if (d < 1) { set_error("fir: decimation %d < 1", d); return SDRGPU_EARG; }
+        return SDRGPU_OK;
+    }
     int setup(int dev, int dtype_, int ttype_, const float* t, int n, int decim) {
         device = dev;
         in_dtype = dtype_;
         out_dtype = quad ? SDRGPU_F32 : (stereo ? SDRGPU_C64 : dtype_);
         ttype = ttype_;
-        if (decim < 1) { set_error("fir: decimation %d < 1", decim); return SDRGPU_EARG; }
+        SDRGPU_CHECK(decim_ok(decim));
         D = decim;
         read_knobs();
-        SDRGPU_CHECK(init_stream());
         return set_taps(t, n);
     }
     // FIR::setTaps (fir.h:31-52): history kept aligned to the newest sample;
     // DecimatingFIR::setTaps resets the decimation phase (decimating_fir.h:19-26)
     int set_taps(const float* t, int n) {
         if (!t || n < 1 || n > 64001) { set_error("fir: tap count %d out of range [1, 64001]", n); return SDRGPU_EARG; }
-        SDRGPU_SET_DEVICE(device);
         const size_t es = esize(in_dtype);
         const int oldH = ntaps > 0 ? ntaps - 1 : 0, newH = n - 1;
         std::vector<unsigned char> oldHist((size_t)oldH * es), newHist((size_t)std::max(newH, 1) * es, 0);
@@ -245,14 +245,13 @@ struct FirBlock : Block {
         return SDRGPU_OK;
     }
     int set_decimation(int d) {
-        if (d < 1) { set_error("fir: decimation %d < 1", d); return SDRGPU_EARG; }
+        SDRGPU_CHECK(decim_ok(d));
         D = d;
         offset = 0;
         return upload_taps();
     }
     // the device tap tables for the current taps / decimation, and the kernel that takes them
     int upload_taps() {
-        SDRGPU_SET_DEVICE(device);
         Q = (qr() + 7) / 8 * 8;      // kernel chunk QC = 8 (zero taps past ntaps)
         const int e = ttype == SDRGPU_C64 ? 2 : 1;
         std::vector<float> pq((size_t)D * Q * e, 0.0f);
@@ -509,7 +508,6 @@ struct FirBlock : Block {
     // ---- one call
     int out_count(int count) override { return count > offset ? (count - offset + D - 1) / D : 0; }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(hist[cur].p, 0, (size_t)std::max(ntaps - 1, 1) * esize(in_dtype)));
         if (quad) SDRGPU_HIP(hipMemset(din[cur].p, 0, sizeof(float2)));
         offset = 0;
@@ -524,7 +522,6 @@ struct FirBlock : Block {
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("fir: negative count"); return SDRGPU_EARG; }
-        SDRGPU_SET_DEVICE(device);
         const int M = out_count(count);
         const int H = ntaps - 1;
         // the row kernel forms its coarse phasors itself (nco_inline); the tile kernels and the
@@ -573,7 +570,6 @@ struct XlatorBlock : Block {
     int out_count(int count) override { return count; }
     int reset() override { nco.phase.reset(); return SDRGPU_OK; }
     int run(const void* in, int count, void* out, hipStream_t s) override {
-        SDRGPU_SET_DEVICE(device);
         if (count > 0) {
             SDRGPU_CHECK(nco.prepare(count, s));
             hipLaunchKernelGGL(xlator_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float2*)in, (float2*)out,
@@ -592,12 +588,10 @@ struct QuadBlock : Block {
     int cur = 0;
     int out_count(int count) override { return count; }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(din[cur].p, 0, sizeof(float2)));
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
-        SDRGPU_SET_DEVICE(device);
         if (count <= 0) return 0;
         hipLaunchKernelGGL(quad_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float2*)in, (float*)out, count,
                            din[cur].as<float2>(), din[cur ^ 1].as<float2>(), invDev);
@@ -612,12 +606,15 @@ struct PolyBlock : Block {
     int interp = 1, decim = 1, tpp = 1, phase = 0, offset = 0;
     DevBuf bank, hist[2];
     int cur = 0;
+    static int args_ok(int ip, int dc, const float* taps, int n) {
+        if (ip < 1 || dc < 1 || !taps || n < 1) { set_error("polyphase: bad ratio/taps"); return SDRGPU_EARG; }
+        return SDRGPU_OK;
+    }
     int setup(int dev, int dtype, int ip, int dc, const float* taps, int n) {
         device = dev;
         in_dtype = out_dtype = dtype;
-        if (ip < 1 || dc < 1 || !taps || n < 1) { set_error("polyphase: bad ratio/taps"); return SDRGPU_EARG; }
+        SDRGPU_CHECK(args_ok(ip, dc, taps, n));
         interp = ip; decim = dc;
-        SDRGPU_CHECK(init_stream());
         // multirate/polyphase_bank.h:15-47: phases[P-1-(i%P)][i/P] = taps[i]
         tpp = (n + interp - 1) / interp;
         std::vector<float> b((size_t)interp * tpp, 0.0f);
@@ -636,13 +633,11 @@ struct PolyBlock : Block {
         return (int)((lim - 1 - pos) / decim + 1);
     }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(hist[cur].p, 0, esize(in_dtype) * std::max(tpp - 1, 1)));
         phase = 0; offset = 0;
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
-        SDRGPU_SET_DEVICE(device);
         const int M = out_count(count);
         const int H = tpp - 1;
         const long long pos0 = (long long)offset * interp + phase;
@@ -850,26 +845,18 @@ static std::unique_ptr<FirBlock> make_fir(int dev, int dtype, int ttype, const f
 static std::unique_ptr<XlatorBlock> make_xlator(int dev, double w, int* rc) {
     auto x = std::make_unique<XlatorBlock>();
     x->device = dev;
-    *rc = x->init_stream();
-    if (*rc >= 0) *rc = x->nco.set_w(w);
+    *rc = x->nco.set_w(w);
     return x;
 }
 template <typename C = ChainBlock>
-static C* new_chain(int dev, int in_dtype, int out_dtype, int* rc) {
+static C* new_chain(int dev, int in_dtype, int out_dtype) {
     auto* c = new C();
     c->device = dev; c->in_dtype = in_dtype; c->out_dtype = out_dtype;
-    *rc = c->init_stream();
     return c;
 }
 
 // composition helpers for other translation units (blocks.h)
-int chain_new(int dev, int in_dtype, int out_dtype, Block** out) {
-    int rc;
-    auto* c = new_chain(dev, in_dtype, out_dtype, &rc);
-    if (rc < 0) { delete c; return rc; }
-    *out = c;
-    return SDRGPU_OK;
-}
+Block* chain_new(int dev, int in_dtype, int out_dtype) { return new_chain(dev, in_dtype, out_dtype); }
 int chain_append(Block* chain, Block* kid) {
     auto* c = dynamic_cast<ChainBlock*>(chain);
     if (!c || !kid) { delete kid; set_error("chain_append: bad argument"); return SDRGPU_EARG; }
@@ -891,7 +878,7 @@ Block* make_quad_block(int dev, double deviationRad, int* rc) {
     auto* q = new QuadBlock();
     q->device = dev; q->in_dtype = SDRGPU_C64; q->out_dtype = SDRGPU_F32;
     q->invDev = (float)(1.0 / deviationRad);
-    *rc = q->init_stream();
+    *rc = SDRGPU_OK;
     for (int k = 0; k < 2 && *rc >= 0; k++) *rc = q->din[k].ensure(sizeof(float2));
     if (*rc >= 0) *rc = q->reset();
     return q;
@@ -902,8 +889,6 @@ Block* make_xlator_block(int dev, double offsetRad, int* rc) {
 int xlator_block_set_offset(Block* xlator, double offsetRad) {
     auto* x = dynamic_cast<XlatorBlock*>(xlator);
     if (!x) { set_error("not an xlator"); return SDRGPU_ESTATE; }
-    SDRGPU_SET_DEVICE(x->device);
-    SDRGPU_HIP(hipDeviceSynchronize());   // (a queued call still reads the fine table that set_w rewrites)
     return x->nco.set_w(xlator_effective_omega(offsetRad));
 }
 
@@ -973,8 +958,8 @@ static int build_rational(ChainBlock* c, int dev, int dtype, double inSr, double
     return SDRGPU_OK;
 }
 Block* make_xlate_resample_block(int dev, double inSr, double outSr, double w, int* rc) {
-    auto* c = new_chain(dev, SDRGPU_C64, SDRGPU_C64, rc);
-    if (*rc >= 0) *rc = build_rational(c, dev, SDRGPU_C64, inSr, outSr, true, w);
+    auto* c = new_chain(dev, SDRGPU_C64, SDRGPU_C64);
+    *rc = build_rational(c, dev, SDRGPU_C64, inSr, outSr, true, w);
     return c;
 }
 
@@ -1017,7 +1002,6 @@ struct WfmBlock : ChainBlock {
         auto* qb = static_cast<QuadBlock*>(kids[0].get());
         auto* fb = static_cast<FirBlock*>(kids[1].get());
         if (count <= 0 || fb->D != 1 || fb->Q % WFM_BK != 0 || fb->Q > 256) return ChainBlock::run(in, count, out, s);
-        SDRGPU_SET_DEVICE(device);
         const bool big = count > kShortMax;
         const auto k = big ? wfm_big_kernel : wfm_short_kernel;
         const int per = big ? WFM_BCH : WFM_TM, threads = big ? WFM_BNT : WFM_TM;   // outputs, threads per workgroup
@@ -1043,7 +1027,6 @@ int vfo_stage1_prepare(sdrgpu_block* vfo, const void* in, int count, VfoStage1* 
     auto* c = vfo_chain(vfo);
     auto* f = vfo_stage1(c);
     if (!f || count <= 0 || !f->rows_external(count)) return 0;
-    SDRGPU_SET_DEVICE(f->device);
     const int M = f->out_count(count);
     SDRGPU_CHECK(c->scratch[0].ensure(sizeof(float2) * (size_t)M));
     st->a = f->rows_args(in, count, c->scratch[0].p, M, f->hist[f->cur ^ 1].p);
@@ -1072,15 +1055,26 @@ int vfo_stage1_finish(sdrgpu_block* vfo, const VfoStage1& st, void* out, hipStre
     return c->run_rest(st.out, st.M, out, s);
 }
 
-// The one way a create function hands a new block to its caller (blocks.h states the ordering rule).
+// The gate of an entry point that takes a block handle (blocks.h states the entry rule).
+int enter_block(::sdrgpu_block* h, bool wait) {
+    if (!h || !h->impl) { set_error("null block handle"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(h->impl->device);
+    if (wait) SDRGPU_HIP(hipDeviceSynchronize());
+    return SDRGPU_OK;
+}
+
+// The one way a create function hands a new block to its caller (blocks.h states the entry and ordering rules).
 int publish_block(::sdrgpu_block** h, Block* b, int rc) {
-    if (rc < 0) { delete b; return rc; }
+    std::unique_ptr<Block> own(b);
+    if (rc < 0) return rc;
+    SDRGPU_SET_DEVICE(b->device);
+    SDRGPU_HIP(hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking));   // the handle's one stream
     // The state written at creation (reset(): memsets / copies on the null stream) must be complete
     // before the first call, which runs on a non-blocking stream the null stream does not order:
     // a handle whose buffer recycled non-zero memory otherwise may start from it (seen once per
     // process on a fresh Quadrature: y[-1] != 0).
-    if (hipDeviceSynchronize() != hipSuccess) { delete b; set_error("hipDeviceSynchronize failed at create"); return SDRGPU_EHIP; }
-    *h = new ::sdrgpu_block{b};
+    if (hipDeviceSynchronize() != hipSuccess) { set_error("hipDeviceSynchronize failed at create"); return SDRGPU_EHIP; }
+    *h = new ::sdrgpu_block{own.release()};
     return SDRGPU_OK;
 }
 
@@ -1094,12 +1088,13 @@ using namespace sdrgpu;
 
 extern "C" int sdrgpu_xlator_create(sdrgpu_block** h, int device, double offsetRad) {
     NEED_OUT(h);
+    SDRGPU_SET_DEVICE(device);
     int rc;
     Block* x = make_xlator_block(device, offsetRad, &rc);
     return publish_block(h, x, rc);
 }
 extern "C" int sdrgpu_xlator_set_offset(sdrgpu_block* h, double offsetRad) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h, true));   // (a queued call still reads the fine table that set_w rewrites)
     return xlator_block_set_offset(h->impl, offsetRad);
 }
 
@@ -1110,18 +1105,21 @@ extern "C" int sdrgpu_fir_create(sdrgpu_block** h, int device, int dtype, int tt
         set_error("fir_create: unsupported (dtype %d, ttype %d)", dtype, ttype);
         return SDRGPU_EARG;
     }
+    SDRGPU_CHECK(FirBlock::decim_ok(decim));
+    SDRGPU_SET_DEVICE(device);
     int rc;
     auto f = make_fir(device, dtype, ttype, taps, ntaps, decim, &rc);
     return publish_block(h, f.release(), rc);
 }
+// the FIR setters read the history back and rewrite it and the tap tables, which a queued call still uses: they wait
 extern "C" int sdrgpu_fir_set_taps(sdrgpu_block* h, const float* taps, int ntaps) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h, true));
     auto* f = dynamic_cast<FirBlock*>(h->impl);
     if (!f) { set_error("not a FIR"); return SDRGPU_ESTATE; }
     return f->set_taps(taps, ntaps);
 }
 extern "C" int sdrgpu_fir_set_decimation(sdrgpu_block* h, int decim) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h, true));
     auto* f = dynamic_cast<FirBlock*>(h->impl);
     if (!f) { set_error("not a FIR"); return SDRGPU_ESTATE; }
     return f->set_decimation(decim);
@@ -1129,6 +1127,7 @@ extern "C" int sdrgpu_fir_set_decimation(sdrgpu_block* h, int decim) {
 
 extern "C" int sdrgpu_quadrature_create(sdrgpu_block** h, int device, double deviationRad) {
     NEED_OUT(h);
+    SDRGPU_SET_DEVICE(device);
     int rc;
     Block* q = make_quad_block(device, deviationRad, &rc);
     return publish_block(h, q, rc);
@@ -1147,37 +1146,36 @@ extern "C" int sdrgpu_power_decimator_create(sdrgpu_block** h, int device, int d
         set_error("power_decimator: ratio %d must be a power of two <= 8192", ratio);   // checkRatio
         return SDRGPU_EARG;
     }
-    int rc;
-    auto* c = new_chain(device, dtype, dtype, &rc);
-    if (rc >= 0) rc = build_power_decim(c, device, dtype, ratio, false, 0.0);
-    return publish_block(h, c, rc);
+    SDRGPU_SET_DEVICE(device);
+    auto* c = new_chain(device, dtype, dtype);
+    return publish_block(h, c, build_power_decim(c, device, dtype, ratio, false, 0.0));
 }
 
 extern "C" int sdrgpu_polyphase_resampler_create(sdrgpu_block** h, int device, int dtype, int interp, int decim,
                                                  const float* taps, int ntaps) {
     NEED_OUT(h);
+    SDRGPU_CHECK(PolyBlock::args_ok(interp, decim, taps, ntaps));
+    SDRGPU_SET_DEVICE(device);
     auto* p = new PolyBlock();
     return publish_block(h, p, p->setup(device, dtype, interp, decim, taps, ntaps));
 }
 
 extern "C" int sdrgpu_rational_resampler_create(sdrgpu_block** h, int device, int dtype, double inSr, double outSr) {
     NEED_OUT(h);
-    int rc;
-    auto* c = new_chain(device, dtype, dtype, &rc);
-    if (rc >= 0) rc = build_rational(c, device, dtype, inSr, outSr, false, 0.0);
-    return publish_block(h, c, rc);
+    SDRGPU_SET_DEVICE(device);
+    auto* c = new_chain(device, dtype, dtype);
+    return publish_block(h, c, build_rational(c, device, dtype, inSr, outSr, false, 0.0));
 }
 
 extern "C" int sdrgpu_rxvfo_create(sdrgpu_block** h, int device, double inSr, double outSr, double bw, double offset) {
     NEED_OUT(h);
-    int rc;
-    auto* v = new_chain<VfoBlock>(device, SDRGPU_C64, SDRGPU_C64, &rc);
+    SDRGPU_SET_DEVICE(device);
+    auto* v = new_chain<VfoBlock>(device, SDRGPU_C64, SDRGPU_C64);
     v->inSr = inSr; v->outSr = outSr; v->bw = bw; v->offset = offset;
-    if (rc >= 0) rc = v->build();
-    return publish_block(h, v, rc);
+    return publish_block(h, v, v->build());
 }
 extern "C" int sdrgpu_rxvfo_set_offset(sdrgpu_block* h, double offset) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h, true));   // (a queued call still reads the NCO tables that set_w rewrites)
     auto* v = dynamic_cast<VfoBlock*>(h->impl);
     if (!v) { set_error("not an RxVFO"); return SDRGPU_ESTATE; }
     return v->set_offset(offset);
@@ -1186,6 +1184,8 @@ extern "C" int sdrgpu_rxvfo_set_offset(sdrgpu_block* h, double offset) {
 extern "C" int sdrgpu_ddc_fm_create(sdrgpu_block** h, int device, double offsetRad, const float* taps, int ntaps, int decim,
                                     double deviationRad) {
     NEED_OUT(h);
+    SDRGPU_CHECK(FirBlock::decim_ok(decim));
+    SDRGPU_SET_DEVICE(device);
     int rc;
     auto f = make_fir(device, SDRGPU_C64, SDRGPU_F32, taps, ntaps, decim, &rc, true, xlator_effective_omega(offsetRad),
                       true, (float)(1.0 / deviationRad));
@@ -1197,6 +1197,8 @@ extern "C" int sdrgpu_ddc_fm_create(sdrgpu_block** h, int device, double offsetR
 // DDC+FM block with the quadrature epilogue off (RxVFO's first stage has this shape too).
 extern "C" int sdrgpu_ddc_create(sdrgpu_block** h, int device, double offsetRad, const float* taps, int ntaps, int decim) {
     NEED_OUT(h);
+    SDRGPU_CHECK(FirBlock::decim_ok(decim));
+    SDRGPU_SET_DEVICE(device);
     int rc;
     auto f = make_fir(device, SDRGPU_C64, SDRGPU_F32, taps, ntaps, decim, &rc, true, xlator_effective_omega(offsetRad));
     return publish_block(h, f.release(), rc);
@@ -1205,9 +1207,10 @@ extern "C" int sdrgpu_ddc_create(sdrgpu_block** h, int device, double offsetRad,
 // FM<float> (demod/fm.h:25-133): quadrature(bw/2) -> optional LPF/HPF/BPF
 extern "C" int sdrgpu_fm_create(sdrgpu_block** h, int device, double samplerate, double bandwidth, int lowPass, int highPass) {
     NEED_OUT(h);
+    SDRGPU_SET_DEVICE(device);
     int rc;
-    auto* c = new_chain(device, SDRGPU_C64, SDRGPU_F32, &rc);
-    if (rc >= 0) c->kids.emplace_back(make_quad_block(device, hz_to_rads(bandwidth / 2.0, samplerate), &rc));
+    auto* c = new_chain(device, SDRGPU_C64, SDRGPU_F32);
+    c->kids.emplace_back(make_quad_block(device, hz_to_rads(bandwidth / 2.0, samplerate), &rc));
     if (rc >= 0 && (lowPass || highPass)) {
         std::vector<float> t;
         rc = (lowPass && highPass) ? design_taps(t, taps_band_pass_f, 300.0, bandwidth / 2.0, 100.0, samplerate, 0)
@@ -1225,9 +1228,10 @@ extern "C" int sdrgpu_fm_create(sdrgpu_block** h, int device, double samplerate,
 // 228-tap (at 240 kS/s) audio LPF lowPass(15 kHz, 4 kHz) -> LRToStereo(l = r)
 extern "C" int sdrgpu_wfm_create(sdrgpu_block** h, int device, double deviation, double samplerate, int lowPass) {
     NEED_OUT(h);
+    SDRGPU_SET_DEVICE(device);
     int rc;
-    auto* c = new_chain<WfmBlock>(device, SDRGPU_C64, SDRGPU_C64, &rc);
-    if (rc >= 0) c->kids.emplace_back(make_quad_block(device, hz_to_rads(deviation, samplerate), &rc));
+    auto* c = new_chain<WfmBlock>(device, SDRGPU_C64, SDRGPU_C64);
+    c->kids.emplace_back(make_quad_block(device, hz_to_rads(deviation, samplerate), &rc));
     if (rc >= 0) {
         std::vector<float> t;
         // unfiltered MPX (or no low-pass at this rate): identity tap, same stereo interleave
@@ -1244,16 +1248,16 @@ extern "C" int sdrgpu_block_out_count(sdrgpu_block* h, int count) {
 }
 
 extern "C" int sdrgpu_block_process_dev(sdrgpu_block* h, const void* in, int count, void* out, void* stream) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h));
     if (count < 0 || (count > 0 && (!in || !out))) { set_error("process: bad buffers"); return SDRGPU_EARG; }
     Block* b = h->impl;
     const hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    SDRGPU_SET_DEVICE(b->device);
     SDRGPU_CHECK(b->order.follow(s));
     OrderScope od(b->order, s);
     return b->run(in, count, out, s);
 }
 
+// (the owner's entry point has selected the device)
 int sdrgpu::block_run_owned(sdrgpu_block* h, const void* in, int count, void* out, hipStream_t s) {
     NEED_HANDLE(h);
     if (count < 0 || (count > 0 && (!in || !out))) { set_error("process: bad buffers"); return SDRGPU_EARG; }
@@ -1261,10 +1265,9 @@ int sdrgpu::block_run_owned(sdrgpu_block* h, const void* in, int count, void* ou
 }
 
 extern "C" int sdrgpu_block_process(sdrgpu_block* h, const void* in, int count, void* out) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h));
     if (count < 0 || (count > 0 && (!in || !out))) { set_error("process: bad buffers"); return SDRGPU_EARG; }
     Block* b = h->impl;
-    SDRGPU_SET_DEVICE(b->device);
     const size_t inB = (size_t)std::max(count, 1) * esize(b->in_dtype);
     const int mExp = b->out_count(count);
     const size_t outB = (size_t)std::max(mExp, 1) * esize(b->out_dtype);
@@ -1292,7 +1295,7 @@ extern "C" int sdrgpu_block_process(sdrgpu_block* h, const void* in, int count, 
 }
 
 extern "C" int sdrgpu_block_reset(sdrgpu_block* h) {
-    NEED_HANDLE(h);
+    SDRGPU_CHECK(enter_block(h, true));   // queued calls still read and write the state that reset() rewrites
     int rc = h->impl->reset();
     if (rc >= 0) SDRGPU_HIP(hipDeviceSynchronize());
     return rc;

@@ -1,5 +1,6 @@
-// Critically sampled M-channel polyphase channelizer (BASELINE config C4): the host side. The
-// kernels and their layout are in chan_kernels.h.
+// Critically sampled M-channel polyphase channelizer (BASELINE config C4): the host side (the block
+// struct, which selects no device and owns no stream, and its create function, which does: blocks.h).
+// The kernels and their layout are in chan_kernels.h.
 //
 // Definition: channel k is FrequencyXlator(-k fs/M)
 // (channel/frequency_xlator.h:43-50, exact NCO) -> DecimatingFIR<complex_t, float>(h, M)
@@ -30,21 +31,12 @@ struct ChannelizerBlock : Block {
     DevBuf taps, tw, hist[2];
     int cur = 0;
 
-    int setup(int dev, int channels, const float* t, int n) {
+    int setup(int dev, int channels, const float* t, int n) {   // (the create function has checked the arguments)
         device = dev;
         in_dtype = out_dtype = SDRGPU_C64;
-        if (channels != 256 && channels != 512 && channels != 1024) {
-            set_error("channelizer: %d channels unsupported (256, 512 or 1024)", channels);
-            return SDRGPU_EARG;
-        }
-        if (!t || n < 1 || n > CHAN_Q * channels) {
-            set_error("channelizer: %d taps out of range [1, %d]", n, CHAN_Q * channels);
-            return SDRGPU_EARG;
-        }
         M = channels;
         ntaps = n;
         Hp = CHAN_Q * M - 1;
-        SDRGPU_CHECK(init_stream());
         std::vector<float> pq((size_t)CHAN_Q * M, 0.0f);       // [q][r] = h[q M + r]
         for (int j = 0; j < n; j++) pq[j] = t[j];
         SDRGPU_CHECK(taps.ensure(sizeof(float) * pq.size()));
@@ -62,7 +54,6 @@ struct ChannelizerBlock : Block {
     // DecimatingFIR output count (decimating_fir.h:45-68) x M channels
     int out_count(int count) override { return count > offset ? (count - offset + M - 1) / M * M : 0; }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(hist[cur].p, 0, sizeof(float2) * Hp));
         offset = 0;
         phase = 0;
@@ -81,7 +72,6 @@ struct ChannelizerBlock : Block {
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("channelizer: negative count"); return SDRGPU_EARG; }
-        SDRGPU_SET_DEVICE(device);
         const int outN = out_count(count);
         const int frames = outN / M;
         const int H = ntaps - 1;                                   // the reference FIR's history
@@ -113,6 +103,15 @@ using namespace sdrgpu;
 
 extern "C" int sdrgpu_channelizer_create(sdrgpu_block** h, int device, int channels, const float* taps, int ntaps) {
     if (!h) { set_error("null out-handle"); return SDRGPU_EARG; }
+    if (channels != 256 && channels != 512 && channels != 1024) {
+        set_error("channelizer: %d channels unsupported (256, 512 or 1024)", channels);
+        return SDRGPU_EARG;
+    }
+    if (!taps || ntaps < 1 || ntaps > CHAN_Q * channels) {
+        set_error("channelizer: %d taps out of range [1, %d]", ntaps, CHAN_Q * channels);
+        return SDRGPU_EARG;
+    }
+    SDRGPU_SET_DEVICE(device);
     auto* b = new ChannelizerBlock();
     return publish_block(h, b, b->setup(device, channels, taps, ntaps));
 }

@@ -2,8 +2,8 @@
 //   noise_reduction::FMIF     noise_reduction/fm_if.h:45-77   ("IF Noise Reduction" of WFM / NFM)
 //   noise_reduction::Squelch  noise_reduction/squelch.h:33-63
 // (noise_reduction::NoiseBlanker is a serial recurrence and lives in loops.hip.) This file is the host
-// side: the two block structs with their launches, then the C entry points; the kernels described
-// below are in ifnr_kernels.h.
+// side: the two block structs with their launches, then the C entry points, which alone select the
+// device and wait for it (blocks.h); the kernels described below are in ifnr_kernels.h.
 //
 // FMIF. With B = bins, w[n] = (float)nuttall(n, B - 1) and buf = [history (B - 1) || in]:
 //   X_i[k] = sum_{n < B} w[n] buf[i + n] e^{-j 2 pi k n / B},   idx_i = argmax_k |X_i[k]| (lowest k on a tie),
@@ -56,30 +56,27 @@ struct FmifBlock : Block {
     int setup(int dev, int bins) {
         device = dev;
         in_dtype = out_dtype = SDRGPU_C64;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(tab.ensure(sizeof(float) * IF_TAB));
         for (int k = 0; k < 2; k++) SDRGPU_CHECK(hist[k].ensure(sizeof(float2) * 32));
         return set_bins(bins);
     }
-    int set_bins(int bins) {   // initBuffers (fm_if.h:92-117): window and zeroed history
+    // initBuffers (fm_if.h:92-117): window and zeroed history. The caller has waited for the device: queued
+    // calls still read the old table.
+    int set_bins(int bins) {
         std::vector<float> t(IF_TAB);
         SDRGPU_CHECK(fmif_tables(bins, t.data(), t.data() + 32 * 32, t.data() + 2 * 32 * 32));
-        SDRGPU_SET_DEVICE(device);
-        SDRGPU_HIP(hipDeviceSynchronize());   // queued calls still read the old table
         SDRGPU_HIP(hipMemcpy(tab.p, t.data(), sizeof(float) * IF_TAB, hipMemcpyHostToDevice));
         B = bins;
         return reset();   // (the caller synchronises: publish_block at create, sdrgpu_fmif_set_bins)
     }
     int out_count(int count) override { return count; }
     int reset() override {   // fm_if.h:36-43
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(hist[cur].p, 0, sizeof(float2) * 32));
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("fmif: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;   // the history is the last B - 1 of [history || nothing]
-        SDRGPU_SET_DEVICE(device);
         FmifArgs a;
         a.in = (const float2*)in;
         a.out = (float2*)out;
@@ -106,20 +103,17 @@ struct SquelchBlock : Block {
         device = dev;
         in_dtype = out_dtype = SDRGPU_C64;
         level = (float)level_;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(SquelchState)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // _isMute = false, cnt = 0
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(state.p, 0, sizeof(SquelchState)));
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("squelch: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;   // (the reference divides by zero here)
-        SDRGPU_SET_DEVICE(device);
         const int nparts = (int)(((long long)count + SQ_CHUNK - 1) / SQ_CHUNK);
         SDRGPU_CHECK(part.ensure(sizeof(float) * nparts));
         hipLaunchKernelGGL(squelch_partial_kernel, dim3(nparts), dim3(SQ_NT), 0, s, (const float2*)in, count, part.as<float>());
@@ -146,6 +140,7 @@ int fmif_bins_ok(int bins, const char* what) {
 extern "C" int sdrgpu_fmif_create(sdrgpu_block** h, int device, int bins) {
     if (!h) { set_error("fmif_create: null handle pointer"); return SDRGPU_EARG; }
     SDRGPU_CHECK(fmif_bins_ok(bins, "fmif_create"));   // before the device is touched
+    SDRGPU_SET_DEVICE(device);
     auto* f = new FmifBlock();
     return publish_block(h, f, f->setup(device, bins));
 }
@@ -153,6 +148,7 @@ extern "C" int sdrgpu_fmif_set_bins(sdrgpu_block* h, int bins) {
     auto* f = h ? dynamic_cast<FmifBlock*>(h->impl) : nullptr;
     if (!f) { set_error("not an FMIF block"); return SDRGPU_EARG; }
     SDRGPU_CHECK(fmif_bins_ok(bins, "fmif_set_bins"));
+    SDRGPU_CHECK(enter_block(h, true));
     SDRGPU_CHECK(f->set_bins(bins));
     SDRGPU_HIP(hipDeviceSynchronize());   // the new table and the cleared history, before the next call (blocks.h)
     return SDRGPU_OK;
@@ -164,6 +160,7 @@ extern "C" int sdrgpu_fmif_window(int bins, float* out) {
 
 extern "C" int sdrgpu_squelch_create(sdrgpu_block** h, int device, double level) {
     if (!h) { set_error("squelch_create: null handle pointer"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* q = new SquelchBlock();
     return publish_block(h, q, q->setup(device, level));
 }
@@ -176,9 +173,8 @@ extern "C" int sdrgpu_squelch_set_level(sdrgpu_block* h, double level) {
 extern "C" int sdrgpu_squelch_get_muted(sdrgpu_block* h, int* muted) {
     auto* q = h ? dynamic_cast<SquelchBlock*>(h->impl) : nullptr;
     if (!q || !muted) { set_error("squelch_get_muted: bad argument"); return SDRGPU_EARG; }
-    SDRGPU_SET_DEVICE(q->device);
+    SDRGPU_CHECK(enter_block(h, true));   // (UI-rate query: waits for the block's queued work)
     SquelchState s;
-    SDRGPU_HIP(hipDeviceSynchronize());   // (UI-rate query: waits for the block's queued work)
     SDRGPU_HIP(hipMemcpy(&s, q->state.p, sizeof(s), hipMemcpyDeviceToHost));
     *muted = s.muted;
     return SDRGPU_OK;

@@ -6,8 +6,9 @@
 //   demod::CW<T>        demod/cw.h:72-85       (xlate tone -> Re -> AGC)
 //   demod::BroadcastFM  demod/broadcast_fm.h   (stereo decoder and RDS branch)
 // Top to bottom: the block structs (each: configuration, state, setup / reset, its launch in run),
-// the chain-building helpers, the C entry points. Handles are published through publish_block
-// (blocks.h), which also states when an entry point synchronises the device.
+// the chain-building helpers, the C entry points. The structs select no device and own no stream: an
+// entry point does, through enter_block or, for a create, itself and publish_block (blocks.h, which
+// also states when an entry point waits for the device).
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -45,14 +46,12 @@ struct AgcBlock : Block {
         in_dtype = out_dtype = dtype;
         set_params(setPoint, attack, decay, maxGain, maxOutputAmp, initGain_);
         p.enabled = 1;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(AgcState)));
         SDRGPU_CHECK(pend.ensure(sizeof(float)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // agc.h:81-86
-        SDRGPU_SET_DEVICE(device);
         AgcState s;
         s.amp = p.setPoint / initGain;
         s.gain = (p.maxGain < initGain) ? p.maxGain : initGain;
@@ -61,17 +60,14 @@ struct AgcBlock : Block {
         return SDRGPU_OK;
     }
     int set_gain(float g) {   // agc.h:31-35, applied at the next process()
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemcpy(pend.p, &g, sizeof(g), hipMemcpyHostToDevice));
         pending = true;
         pendingGain = g;
         return SDRGPU_OK;
     }
-    int get_gain(float* gain) {
+    int get_gain(float* gain) {   // (the caller has waited for the block's queued work unless `pending`)
         if (pending) { *gain = pendingGain; return SDRGPU_OK; }
-        SDRGPU_SET_DEVICE(device);
         AgcState s;
-        SDRGPU_HIP(hipDeviceSynchronize());   // (UI-rate query: waits for the block's queued work)
         SDRGPU_HIP(hipMemcpy(&s, state.p, sizeof(s), hipMemcpyDeviceToHost));
         *gain = s.gain;
         return SDRGPU_OK;
@@ -85,7 +81,6 @@ struct AgcBlock : Block {
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("agc: negative count"); return SDRGPU_EARG; }
-        SDRGPU_SET_DEVICE(device);
         const float* pg = pending ? pend.as<float>() : nullptr;
         pending = false;
         if (count == 0 && !pg) return 0;
@@ -105,13 +100,11 @@ struct DcbBlock : Block {
         device = dev;
         in_dtype = out_dtype = dtype;
         rate = (float)r;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(float2)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(state.p, 0, sizeof(float2)));
         return SDRGPU_OK;
     }
@@ -122,7 +115,6 @@ struct DcbBlock : Block {
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("dc_blocker: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;
-        SDRGPU_SET_DEVICE(device);
         if (in_dtype == SDRGPU_C64) run_t<float2>(in, count, out, s);
         else run_t<float>(in, count, out, s);
         SDRGPU_HIP(hipGetLastError());
@@ -142,13 +134,11 @@ struct NoiseBlankerBlock : Block {
         device = dev;
         in_dtype = out_dtype = SDRGPU_C64;
         set(rate, level);
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(float)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // noise_blanker.h:32-36
-        SDRGPU_SET_DEVICE(device);
         const float one = 1.0f;
         SDRGPU_HIP(hipMemcpy(state.p, &one, sizeof(one), hipMemcpyHostToDevice));
         return SDRGPU_OK;
@@ -156,7 +146,6 @@ struct NoiseBlankerBlock : Block {
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("noise_blanker: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;
-        SDRGPU_SET_DEVICE(device);
         hipLaunchKernelGGL(noise_blanker_kernel, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, p,
                            state.as<float>());
         SDRGPU_HIP(hipGetLastError());
@@ -171,7 +160,6 @@ struct DeempBlock : Block {
         device = dev;
         in_dtype = out_dtype = dtype;                 // F32 (float) or C64 (stereo_t)
         set_alpha(tau, samplerate);
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(float2)));
         return reset();
     }
@@ -181,7 +169,6 @@ struct DeempBlock : Block {
     }
     int out_count(int count) override { return count; }
     int reset() override {
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemset(state.p, 0, sizeof(float2)));
         return SDRGPU_OK;
     }
@@ -192,7 +179,6 @@ struct DeempBlock : Block {
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("deemphasis: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;     // (the reference reads out[-1] for count == 0)
-        SDRGPU_SET_DEVICE(device);
         if (in_dtype == SDRGPU_C64) run_t<2>(in, count, out, s);
         else run_t<1>(in, count, out, s);
         SDRGPU_HIP(hipGetLastError());
@@ -208,7 +194,6 @@ struct MapBlock : Block {
     int reset() override { return SDRGPU_OK; }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count <= 0) return count < 0 ? SDRGPU_EARG : 0;
-        SDRGPU_SET_DEVICE(device);
         const dim3 g((count + 255) / 256), b(256);
         switch (kind) {
         case MapKind::Magnitude: hipLaunchKernelGGL(magnitude_kernel, g, b, 0, s, (const float2*)in, (float*)out, count); break;
@@ -257,7 +242,6 @@ struct BroadcastFmBlock : Block {
         stereo = st;
         lowPass = lp;
         fs = samplerate;
-        SDRGPU_CHECK(init_stream());
         int rc;
         quad.reset(make_quad_block(dev, hz_to_rads(deviation, samplerate), &rc));
         SDRGPU_CHECK(rc);
@@ -289,7 +273,6 @@ struct BroadcastFmBlock : Block {
     }
     int out_count(int count) override { return count; }
     int reset() override {   // broadcast_fm.h:129-141
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_CHECK(quad->reset());
         SDRGPU_CHECK(pilot->reset());
         SDRGPU_CHECK(audio->reset());
@@ -303,7 +286,6 @@ struct BroadcastFmBlock : Block {
         if (count < 0) { set_error("broadcast_fm: negative count"); return SDRGPU_EARG; }
         rdsN = 0;
         if (count == 0) return 0;
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_CHECK(mpx.ensure(sizeof(float) * count));
         SDRGPU_CHECK(lr.ensure(sizeof(float2) * count));
         int m = quad->run(in, count, mpx.p, s);
@@ -367,8 +349,8 @@ static AgcBlock* make_demod_agc(int dev, int dtype, double attack, double decay,
 // xlate -> Re -> AGC [-> MonoToStereo] (ssb.h:90-105, cw.h:72-85) into the new chain *c; *xl: its xlator
 static int xlate_agc_chain(int device, double offsetRad, bool agcEnabled, double attack, double decay, double maxOutputAmp,
                            double initGain, bool stereo, Block** c, Block** xl = nullptr) {
-    int rc = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32, c);
-    if (rc < 0) return rc;
+    *c = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32);
+    int rc;
     Block* x = make_xlator_block(device, offsetRad, &rc);
     if (xl) *xl = x;
     rc = append_owned(*c, x, rc);
@@ -406,6 +388,7 @@ using namespace sdrgpu;
 extern "C" int sdrgpu_agc_create(sdrgpu_block** h, int device, int dtype, double setPoint, double attack, double decay,
                                  double maxGain, double maxOutputAmp, double initGain) {
     if (!h || (dtype != SDRGPU_F32 && dtype != SDRGPU_C64)) { set_error("agc_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* a = new AgcBlock();
     return publish_block(h, a, a->setup(device, dtype, setPoint, attack, decay, maxGain, maxOutputAmp, initGain));
 }
@@ -426,16 +409,19 @@ extern "C" int sdrgpu_agc_set_enabled(sdrgpu_block* h, int enabled) {
 extern "C" int sdrgpu_agc_set_gain(sdrgpu_block* h, float gain) {
     auto* a = h ? dynamic_cast<AgcBlock*>(h->impl) : nullptr;
     if (!a) { set_error("not an AGC"); return SDRGPU_EARG; }
+    SDRGPU_CHECK(enter_block(h, true));   // (a queued call may still read the latched gain's device word)
     return a->set_gain(gain);
 }
 extern "C" int sdrgpu_agc_get_gain(sdrgpu_block* h, float* gain) {
     auto* a = h ? dynamic_cast<AgcBlock*>(h->impl) : nullptr;
     if (!a || !gain) { set_error("agc_get_gain: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_CHECK(enter_block(h, !a->pending));   // (UI-rate query: waits for the block's queued work)
     return a->get_gain(gain);
 }
 
 extern "C" int sdrgpu_dc_blocker_create(sdrgpu_block** h, int device, int dtype, double rate) {
     if (!h || (dtype != SDRGPU_F32 && dtype != SDRGPU_C64)) { set_error("dc_blocker_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* d = new DcbBlock();
     return publish_block(h, d, d->setup(device, dtype, rate));
 }
@@ -450,6 +436,7 @@ extern "C" int sdrgpu_dc_blocker_set_rate(sdrgpu_block* h, double rate) {
 // noise_reduction::NoiseBlanker (noise_blanker.h): the setters keep the running amplitude
 extern "C" int sdrgpu_noise_blanker_create(sdrgpu_block** h, int device, double rate, double level) {
     if (!h) { set_error("noise_blanker_create: null handle pointer"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* b = new NoiseBlankerBlock();
     return publish_block(h, b, b->setup(device, rate, level));
 }
@@ -463,6 +450,7 @@ extern "C" int sdrgpu_noise_blanker_set(sdrgpu_block* h, double rate, double lev
 // filter::Deemphasis<T> (deephasis.h): dtype F32 (float) or C64 (stereo_t)
 extern "C" int sdrgpu_deemphasis_create(sdrgpu_block** h, int device, int dtype, double tau, double samplerate) {
     if (!h || (dtype != SDRGPU_F32 && dtype != SDRGPU_C64) || !(samplerate > 0)) { set_error("deemphasis_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* d = new DeempBlock();
     return publish_block(h, d, d->setup(device, dtype, tau, samplerate));
 }
@@ -477,9 +465,9 @@ extern "C" int sdrgpu_deemphasis_set(sdrgpu_block* h, double tau, double sampler
 extern "C" int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, double bandwidth, double agcAttack,
                                 double agcDecay, double dcBlockRate, double samplerate, int stereo) {
     if (!h || agcMode < 0 || agcMode > 2) { set_error("am_create: bad argument"); return SDRGPU_EARG; }
-    Block* c = nullptr;
-    int rc = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32, &c);
-    if (rc < 0) return rc;
+    SDRGPU_SET_DEVICE(device);
+    Block* c = chain_new(device, SDRGPU_C64, stereo ? SDRGPU_C64 : SDRGPU_F32);
+    int rc = SDRGPU_OK;
     if (agcMode == 1) {
         Block* a = make_demod_agc(device, SDRGPU_C64, agcAttack, agcDecay, true, &rc);
         rc = append_owned(c, a, rc);
@@ -509,6 +497,7 @@ extern "C" int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, doubl
 extern "C" int sdrgpu_ssb_create(sdrgpu_block** h, int device, int mode, double bandwidth, double samplerate,
                                  int agcEnabled, double agcAttack, double agcDecay, int stereo) {
     if (!h || mode < 0 || mode > 2) { set_error("ssb_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     Block* c = nullptr;
     const double tr = mode == 0 ? bandwidth / 2.0 : (mode == 1 ? -bandwidth / 2.0 : 0.0);   // getTranslation
     const int rc = xlate_agc_chain(device, hz_to_rads(tr, samplerate), agcEnabled != 0, agcAttack, agcDecay, 10.0, INFINITY, stereo != 0, &c);
@@ -520,15 +509,15 @@ extern "C" int sdrgpu_ssb_create(sdrgpu_block** h, int device, int mode, double 
 extern "C" int sdrgpu_cw_create(sdrgpu_block** h, int device, double tone, int agcEnabled, double agcAttack, double agcDecay,
                                 double samplerate, int stereo) {
     if (!h || !std::isfinite(tone) || !std::isfinite(samplerate) || !(samplerate > 0)) { set_error("cw_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* w = new CwBlock();
     w->device = device;
     w->in_dtype = SDRGPU_C64;
     w->out_dtype = stereo ? SDRGPU_C64 : SDRGPU_F32;
     w->samplerate = samplerate;
     Block* c = nullptr;
-    int rc = xlate_agc_chain(device, hz_to_rads(tone, samplerate), agcEnabled != 0, agcAttack, agcDecay, 1.0, 1.0, stereo != 0, &c, &w->xlator);
+    const int rc = xlate_agc_chain(device, hz_to_rads(tone, samplerate), agcEnabled != 0, agcAttack, agcDecay, 1.0, 1.0, stereo != 0, &c, &w->xlator);
     w->chain.reset(c);
-    if (rc >= 0) rc = w->init_stream();
     return publish_block(h, w, rc);
 }
 // CW::setTone (cw.h:30-35): the xlator's offset changes, its phase is kept
@@ -537,17 +526,21 @@ extern "C" int sdrgpu_cw_set_tone(sdrgpu_block* h, double tone) {
     auto* w = dynamic_cast<CwBlock*>(h->impl);
     if (!w) { set_error("not a CW block"); return SDRGPU_ESTATE; }
     if (!std::isfinite(tone)) { set_error("cw_set_tone: tone not finite"); return SDRGPU_EARG; }
+    SDRGPU_CHECK(enter_block(h, true));   // (a queued call still reads the fine table that the setter rewrites)
     return xlator_block_set_offset(w->xlator, hz_to_rads(tone, w->samplerate));
 }
 
 extern "C" int sdrgpu_demod_agc_set_gain(sdrgpu_block* h, int which, float gain) {
     AgcBlock* a = demod_agc(h, which);
-    return a ? a->set_gain(gain) : SDRGPU_ESTATE;
+    if (!a) return SDRGPU_ESTATE;
+    SDRGPU_CHECK(enter_block(h, true));
+    return a->set_gain(gain);
 }
 extern "C" int sdrgpu_demod_agc_get_gain(sdrgpu_block* h, int which, float* gain) {
     AgcBlock* a = demod_agc(h, which);
     if (!a) return SDRGPU_ESTATE;
     if (!gain) { set_error("agc_get_gain: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_CHECK(enter_block(h, !a->pending));
     return a->get_gain(gain);
 }
 extern "C" int sdrgpu_demod_agc_set_enabled(sdrgpu_block* h, int which, int enabled) {
@@ -569,13 +562,14 @@ extern "C" int sdrgpu_demod_agc_set_attack_decay(sdrgpu_block* h, double attack,
 extern "C" int sdrgpu_broadcast_fm_create(sdrgpu_block** h, int device, double deviation, double samplerate, int stereo,
                                           int lowPass) {
     if (!h || !(samplerate > 0)) { set_error("broadcast_fm_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* w = new BroadcastFmBlock();
     return publish_block(h, w, w->setup(device, deviation, samplerate, stereo != 0, lowPass != 0));
 }
 extern "C" int sdrgpu_broadcast_fm_set_rds(sdrgpu_block* h, int enabled) {   // setRDSOut (broadcast_fm.h:121-127)
     auto* w = h ? dynamic_cast<BroadcastFmBlock*>(h->impl) : nullptr;
     if (!w) { set_error("not a broadcast_fm block"); return SDRGPU_EARG; }
-    SDRGPU_SET_DEVICE(w->device);
+    SDRGPU_CHECK(enter_block(h));
     const bool built = enabled && !w->rdsChain;
     SDRGPU_CHECK(w->set_rds(enabled != 0));
     if (built) SDRGPU_HIP(hipDeviceSynchronize());   // the new RDS chain's histories, zeroed on the null stream (blocks.h)
@@ -594,8 +588,7 @@ extern "C" int sdrgpu_broadcast_fm_read_rds(sdrgpu_block* h, void* out, int max)
     if (!w || (!out && max > 0)) { set_error("broadcast_fm_read_rds: bad argument"); return SDRGPU_EARG; }
     const int n = std::min(max, w->rds ? w->rdsN : 0);
     if (n <= 0) return 0;
-    SDRGPU_SET_DEVICE(w->device);
-    SDRGPU_HIP(hipDeviceSynchronize());
+    SDRGPU_CHECK(enter_block(h, true));
     SDRGPU_HIP(hipMemcpy(out, w->rdsOut.p, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost));
     return n;
 }

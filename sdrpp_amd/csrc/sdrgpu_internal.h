@@ -125,12 +125,11 @@ struct PhaseAcc {
 struct Block {
     int device = 0;
     int in_dtype = SDRGPU_C64, out_dtype = SDRGPU_C64;
-    hipStream_t own = nullptr;
+    hipStream_t own = nullptr;   // a handle's block only (publish_block); a chain's kids have none
     PinnedBuf pin_in, pin_out;
     DevBuf dev_in, dev_out;
     StreamOrder order;   // entry points (process / process_dev) only; sub-blocks share the caller's stream
     virtual ~Block();
-    int init_stream();
     // exact number of outputs the next process() of `count` inputs yields
     virtual int out_count(int count) = 0;
     // asynchronous device-side processing on `s`; returns the output count

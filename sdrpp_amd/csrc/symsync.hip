@@ -6,8 +6,9 @@
 //   demod::GFSK         demod/gfsk.h:24-41, 131-135  (Quadrature -> RRC FIR -> MM<float>)
 //   the RDS chain       decoder_modules/radio/src/demodulators/wfm.h:57-68
 // Top to bottom: the block structs (each: configuration, state, setup / reset, its launch in run), the
-// C entry points. Handles are published through publish_block (blocks.h), which also states when an
-// entry point synchronises the device.
+// C entry points. The structs select no device and own no stream: an entry point does, through
+// enter_block or, for a create, itself and publish_block (blocks.h, which also states when an entry
+// point waits for the device).
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -30,13 +31,11 @@ struct FastAgcBlock : Block {
         device = dev;
         in_dtype = out_dtype = dtype;
         set(setPoint, maxGain, rate, initGain_);
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(float)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // fast_agc.h:54-58
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemcpy(state.p, &initGain, sizeof(float), hipMemcpyHostToDevice));
         p.hasGain = 0;
         return SDRGPU_OK;
@@ -45,17 +44,14 @@ struct FastAgcBlock : Block {
         p.setGain = (float)g;
         p.hasGain = 1;
     }
-    int get_gain(float* gain) {
+    int get_gain(float* gain) {   // (the caller has waited for the block's queued work unless a gain is latched)
         if (p.hasGain) { *gain = p.setGain; return SDRGPU_OK; }
-        SDRGPU_SET_DEVICE(device);
-        SDRGPU_HIP(hipDeviceSynchronize());   // (UI-rate query: waits for the block's queued work)
         SDRGPU_HIP(hipMemcpy(gain, state.p, sizeof(float), hipMemcpyDeviceToHost));
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("fast_agc: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;   // (a latched gain waits for the next samples)
-        SDRGPU_SET_DEVICE(device);
         if (in_dtype == SDRGPU_C64)
             hipLaunchKernelGGL(fast_agc_kernel<float2>, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, p, state.as<float>());
         else
@@ -80,13 +76,11 @@ struct CostasBlock : Block {
         p.pcl.maxFreq = (float)maxFreq;
         initPhase = (float)initPhase_;
         initFreq = (float)initFreq_;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(float2)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // pll.h:55-62
-        SDRGPU_SET_DEVICE(device);
         const float2 st = make_float2(initPhase, initFreq);
         SDRGPU_HIP(hipMemcpy(state.p, &st, sizeof(st), hipMemcpyHostToDevice));
         return SDRGPU_OK;
@@ -98,7 +92,6 @@ struct CostasBlock : Block {
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count < 0) { set_error("costas: negative count"); return SDRGPU_EARG; }
         if (count == 0) return 0;
-        SDRGPU_SET_DEVICE(device);
         if (order == 2) run_t<2>(in, count, out, s);
         else if (order == 4) run_t<4>(in, count, out, s);
         else run_t<8>(in, count, out, s);
@@ -130,7 +123,6 @@ struct MmBlock : Block {
         p.modulus = 2;
         std::vector<float> b((size_t)P * T);
         SDRGPU_CHECK(mm_interp_bank(P, T, b.data()));
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(state.ensure(sizeof(MmState)));
         SDRGPU_CHECK(hist.ensure(esize(dtype) * std::max(T - 1, 1)));
         SDRGPU_CHECK(bank.ensure(sizeof(float) * b.size()));
@@ -142,7 +134,6 @@ struct MmBlock : Block {
     // the capacity of a call: at most one output per input sample (mm_params_ok)
     int out_count(int count) override { return count; }
     int reset() override {   // mm.h:87-98: the state, not the history
-        SDRGPU_SET_DEVICE(device);
         MmState s{};
         s.freq = (float)omega;
         SDRGPU_HIP(hipMemcpy(state.p, &s, sizeof(s), hipMemcpyHostToDevice));
@@ -159,7 +150,6 @@ struct MmBlock : Block {
         if (count < 0) { set_error("mm: negative count"); return SDRGPU_EARG; }
         lastCount = 0;
         if (count == 0) return 0;   // (latched setters wait for the next samples)
-        SDRGPU_SET_DEVICE(device);
         if (epi == MmEpilogue::DiffBits) {
             SDRGPU_CHECK(soft.ensure(sizeof(float) * (size_t)count));
             run_t<float, MmEpilogue::DiffBits>(in, count, out, s);
@@ -183,7 +173,6 @@ struct SlicerBlock : Block {
     int reset() override { return SDRGPU_OK; }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count <= 0) return count < 0 ? SDRGPU_EARG : 0;
-        SDRGPU_SET_DEVICE(device);
         hipLaunchKernelGGL(slicer_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const float*)in, (uint8_t*)out, count);
         SDRGPU_HIP(hipGetLastError());
         return count;
@@ -199,19 +188,16 @@ struct DiffDecoderBlock : Block {
         in_dtype = out_dtype = SDRGPU_U8;
         modulus = modulus_;
         initSym = initSym_;
-        SDRGPU_CHECK(init_stream());
         SDRGPU_CHECK(last.ensure(2 * sizeof(int)));
         return reset();
     }
     int out_count(int count) override { return count; }
     int reset() override {   // differential_decoder.h:33-39
-        SDRGPU_SET_DEVICE(device);
         SDRGPU_HIP(hipMemcpy(last.as<int>() + cur, &initSym, sizeof(int), hipMemcpyHostToDevice));
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
         if (count <= 0) return count < 0 ? SDRGPU_EARG : 0;
-        SDRGPU_SET_DEVICE(device);
         hipLaunchKernelGGL(diff_decode_kernel, dim3((count + 255) / 256), dim3(256), 0, s, (const uint8_t*)in, (uint8_t*)out, count,
                            modulus, last.as<int>() + cur, last.as<int>() + (cur ^ 1));
         cur ^= 1;
@@ -229,21 +215,15 @@ static Block* make_fast_agc(int dev, int dtype, double setPoint, double maxGain,
 static Block* make_costas(int dev, int order, double bandwidth, double initPhase, double initFreq, double minFreq,
                           double maxFreq, int* rc) {
     auto* c = new CostasBlock();
-    if (!costas_args_ok(order, bandwidth, initPhase, initFreq, minFreq, maxFreq)) {
-        *rc = SDRGPU_EARG;
-        return c;
-    }
-    *rc = c->setup(dev, order, bandwidth, initPhase, initFreq, minFreq, maxFreq);
+    *rc = costas_args_ok(order, bandwidth, initPhase, initFreq, minFreq, maxFreq)
+              ? c->setup(dev, order, bandwidth, initPhase, initFreq, minFreq, maxFreq) : SDRGPU_EARG;
     return c;
 }
 static Block* make_mm(int dev, int dtype, MmEpilogue e, int inStride, double omega, double omegaGain, double muGain, double rel,
                       int P, int T, int* rc) {
     auto* m = new MmBlock();
-    if (!mm_args_ok(omega, omegaGain, muGain, rel, P, T)) {
-        *rc = SDRGPU_EARG;
-    } else {
-        *rc = m->setup(dev, dtype, e, inStride, omega, omegaGain, muGain, rel, P, T);
-    }
+    *rc = mm_args_ok(omega, omegaGain, muGain, rel, P, T) ? m->setup(dev, dtype, e, inStride, omega, omegaGain, muGain, rel, P, T)
+                                                          : SDRGPU_EARG;
     return m;
 }
 // FIR<T, float>(rootRaisedCosine<float>(count, beta, symbolrate, samplerate)) (psk.h:31-32, gfsk.h:32-33)
@@ -271,6 +251,7 @@ using namespace sdrgpu;
 extern "C" int sdrgpu_fast_agc_create(sdrgpu_block** h, int device, int dtype, double setPoint, double maxGain, double rate,
                                       double initGain) {
     if (!h || !real_or_complex(dtype)) { set_error("fast_agc_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     int rc;
     Block* a = make_fast_agc(device, dtype, setPoint, maxGain, rate, initGain, &rc);
     return publish_block(h, a, rc);
@@ -290,15 +271,17 @@ extern "C" int sdrgpu_fast_agc_set_gain(sdrgpu_block* h, double gain) {
 extern "C" int sdrgpu_fast_agc_get_gain(sdrgpu_block* h, float* gain) {
     auto* a = as_block<FastAgcBlock>(h, "a FastAGC");
     if (!a || !gain) { if (a) set_error("fast_agc_get_gain: null pointer"); return SDRGPU_EARG; }
+    SDRGPU_CHECK(enter_block(h, !a->p.hasGain));   // (UI-rate query: waits for the block's queued work)
     return a->get_gain(gain);
 }
 
 extern "C" int sdrgpu_costas_create(sdrgpu_block** h, int device, int order, double bandwidth, double initPhase, double initFreq,
                                     double minFreq, double maxFreq) {
     if (!h) { set_error("costas_create: null handle pointer"); return SDRGPU_EARG; }
-    int rc;
-    Block* c = make_costas(device, order, bandwidth, initPhase, initFreq, minFreq, maxFreq, &rc);
-    return publish_block(h, c, rc);
+    if (!costas_args_ok(order, bandwidth, initPhase, initFreq, minFreq, maxFreq)) return SDRGPU_EARG;   // before the device is touched
+    SDRGPU_SET_DEVICE(device);
+    auto* c = new CostasBlock();
+    return publish_block(h, c, c->setup(device, order, bandwidth, initPhase, initFreq, minFreq, maxFreq));
 }
 extern "C" int sdrgpu_costas_set_bandwidth(sdrgpu_block* h, double bandwidth) {
     auto* c = as_block<CostasBlock>(h, "a Costas loop");
@@ -319,9 +302,10 @@ extern "C" int sdrgpu_costas_set_freq_limits(sdrgpu_block* h, double minFreq, do
 extern "C" int sdrgpu_mm_create(sdrgpu_block** h, int device, int dtype, double omega, double omegaGain, double muGain,
                                 double omegaRelLimit, int interpPhases, int interpTaps) {
     if (!h || !real_or_complex(dtype)) { set_error("mm_create: bad argument"); return SDRGPU_EARG; }
-    int rc;
-    Block* m = make_mm(device, dtype, MmEpilogue::Soft, 1, omega, omegaGain, muGain, omegaRelLimit, interpPhases, interpTaps, &rc);
-    return publish_block(h, m, rc);
+    if (!mm_args_ok(omega, omegaGain, muGain, omegaRelLimit, interpPhases, interpTaps)) return SDRGPU_EARG;   // before the device is touched
+    SDRGPU_SET_DEVICE(device);
+    auto* m = new MmBlock();
+    return publish_block(h, m, m->setup(device, dtype, MmEpilogue::Soft, 1, omega, omegaGain, muGain, omegaRelLimit, interpPhases, interpTaps));
 }
 // the MM setters: on an MM handle, or on a PSK / GFSK / RDS handle (its last block)
 static int mm_set(sdrgpu_block* h, double omega, double omegaGain, double muGain, double rel, bool newOmega) {
@@ -356,14 +340,16 @@ extern "C" int sdrgpu_mm_set_omega_rel_limit(sdrgpu_block* h, double omegaRelLim
 
 extern "C" int sdrgpu_binary_slicer_create(sdrgpu_block** h, int device) {
     if (!h) { set_error("binary_slicer_create: null handle pointer"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* b = new SlicerBlock();
     b->device = device;
     b->in_dtype = SDRGPU_F32;
     b->out_dtype = SDRGPU_U8;
-    return publish_block(h, b, b->init_stream());
+    return publish_block(h, b, SDRGPU_OK);
 }
 extern "C" int sdrgpu_differential_decoder_create(sdrgpu_block** h, int device, int modulus, int initSym) {
     if (!h || modulus < 1 || modulus > 255 || initSym < 0 || initSym > 255) { set_error("differential_decoder_create: bad argument"); return SDRGPU_EARG; }
+    SDRGPU_SET_DEVICE(device);
     auto* d = new DiffDecoderBlock();
     return publish_block(h, d, d->setup(device, modulus, initSym));
 }
@@ -372,9 +358,9 @@ extern "C" int sdrgpu_psk_create(sdrgpu_block** h, int device, int order, double
                                  double rrcBeta, double agcRate, double costasBandwidth, double omegaGain, double muGain,
                                  double omegaRelLimit) {
     if (!h || !(symbolrate > 0) || !(samplerate > 0)) { set_error("psk_create: bad argument"); return SDRGPU_EARG; }
-    Block* c = nullptr;
-    int rc = chain_new(device, SDRGPU_C64, SDRGPU_C64, &c);
-    if (rc < 0) return rc;
+    SDRGPU_SET_DEVICE(device);
+    Block* c = chain_new(device, SDRGPU_C64, SDRGPU_C64);
+    int rc;
     Block* b = make_rrc_fir(device, SDRGPU_C64, rrcTapCount, rrcBeta, symbolrate, samplerate, &rc);
     rc = append_owned(c, b, rc);
     if (rc >= 0) { b = make_fast_agc(device, SDRGPU_C64, 1.0, 10e6, agcRate, 1.0, &rc); rc = append_owned(c, b, rc); }
@@ -390,9 +376,9 @@ extern "C" int sdrgpu_psk_create(sdrgpu_block** h, int device, int order, double
 extern "C" int sdrgpu_gfsk_create(sdrgpu_block** h, int device, double symbolrate, double samplerate, double deviation,
                                   int rrcTapCount, double rrcBeta, double omegaGain, double muGain, double omegaRelLimit) {
     if (!h || !(symbolrate > 0) || !(samplerate > 0)) { set_error("gfsk_create: bad argument"); return SDRGPU_EARG; }
-    Block* c = nullptr;
-    int rc = chain_new(device, SDRGPU_C64, SDRGPU_F32, &c);
-    if (rc < 0) return rc;
+    SDRGPU_SET_DEVICE(device);
+    Block* c = chain_new(device, SDRGPU_C64, SDRGPU_F32);
+    int rc;
     Block* b = make_quad_block(device, hz_to_rads(deviation, samplerate), &rc);   // Quadrature::init(in, deviation, samplerate)
     rc = append_owned(c, b, rc);
     if (rc >= 0) { b = make_rrc_fir(device, SDRGPU_F32, rrcTapCount, rrcBeta, symbolrate, samplerate, &rc); rc = append_owned(c, b, rc); }
@@ -406,9 +392,9 @@ extern "C" int sdrgpu_gfsk_create(sdrgpu_block** h, int device, double symbolrat
 // wfm.h:57-68
 extern "C" int sdrgpu_rds_create(sdrgpu_block** h, int device) {
     if (!h) { set_error("rds_create: null handle pointer"); return SDRGPU_EARG; }
-    Block* c = nullptr;
-    int rc = chain_new(device, SDRGPU_C64, SDRGPU_U8, &c);
-    if (rc < 0) return rc;
+    SDRGPU_SET_DEVICE(device);
+    Block* c = chain_new(device, SDRGPU_C64, SDRGPU_U8);
+    int rc;
     const double PI = 3.1415926535f;
     Block* b = make_fast_agc(device, SDRGPU_C64, 1.0, 1e6, 0.1, 1.0, &rc);
     rc = append_owned(c, b, rc);
