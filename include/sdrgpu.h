@@ -359,7 +359,7 @@ typedef struct sdrgpu_bank sdrgpu_bank;
  * 0 after create / reset */
 int sdrgpu_bank_quadrature_create(sdrgpu_bank** h, int device, int streams, double deviationRad);
 /* filter::FIR<D, float> per stream (filter/fir.h:60-80): real taps shared by all streams, dtype F32 or
- * C64, no decimation; out[m*S + k] = sum_j buf_k[m + j] * taps[j] over [ntaps - 1 history rows || new],
+ * C64, no decimation (sdrgpu_bank_decimating_fir_create has it); out[m*S + k] = sum_j buf_k[m + j] * taps[j] over [ntaps - 1 history rows || new],
  * taps not reversed, summed in ascending tap order in fp32 without contraction (not bit-identical to
  * sdrgpu_fir_create, whose kernel and summation order depend on the shape); history zero at create / reset */
 int sdrgpu_bank_fir_create(sdrgpu_bank** h, int device, int streams, int dtype, const float* taps, int ntaps);
@@ -449,11 +449,42 @@ int sdrgpu_bank_ssb_create(sdrgpu_bank** h, int device, int streams, int mode, d
 int sdrgpu_bank_cw_create(sdrgpu_bank** h, int device, int streams, double tone, int agcEnabled, double agcAttack,
                           double agcDecay, double samplerate);
 
+/* -- rate-changing banks: a bank that writes another number of rows than it reads. All streams
+ * share the ratio and start together, so they share one decimation phase and one row count: counts[k] is the
+ * rows returned for every k, and sdrgpu_bank_out_rows(frames) is exact. dtype F32 or C64 (stereo_t is C64); real
+ * taps shared by all streams; sums in ascending tap order in fp32 without contraction, as sdrgpu_bank_fir_create;
+ * history zero at create / reset, which also zeroes phase and offset. Every call is asynchronous on its
+ * stream; a call of 0 frames, or one that yields no row, changes only the carried phase and history. At a call,
+ * rows in or rows out (of any stage) times streams beyond INT_MAX is SDRGPU_EARG. */
+/* filter::DecimatingFIR<D, float> per stream (filter/decimating_fir.h:45-68): out[j*S + k] = sum_t buf_k[offset +
+ * j*decim + t] * taps[t] over [ntaps - 1 history rows || new], taps not reversed, offset carried as the
+ * reference does (offset -= count); bit-identical to rows [offset :: decim] of sdrgpu_bank_fir_create's output.
+ * decim < 1, or (ntaps - 1) * streams beyond INT_MAX: SDRGPU_EARG */
+int sdrgpu_bank_decimating_fir_create(sdrgpu_bank** h, int device, int streams, int dtype, const float* taps, int ntaps, int decim);
+/* multirate::PolyphaseResampler<T> per stream (multirate/polyphase_resampler.h:69-99) over the bank of
+ * multirate/polyphase_bank.h:15-47 (phases[P-1-(i%P)][i/P] = taps[i], zero-padded to ceil(ntaps / interp) per
+ * phase); interp = 1 is bit-identical to the decimating FIR bank. interp or decim < 1, history rows * streams or
+ * interp * taps-per-phase beyond INT_MAX: SDRGPU_EARG */
+int sdrgpu_bank_polyphase_resampler_create(sdrgpu_bank** h, int device, int streams, int dtype, int interp, int decim,
+                                           const float* taps, int ntaps);
+/* multirate::PowerDecimator<T> per stream (multirate/power_decimator.h:51-108): the stages of
+ * sdrgpu_decim_plan(ratio) as decimating FIR banks one after another, bit-identical to them; ratio 1 copies;
+ * a ratio the plan refuses: SDRGPU_EARG */
+int sdrgpu_bank_power_decimator_create(sdrgpu_bank** h, int device, int streams, int dtype, int ratio);
+/* multirate::RationalResampler<T> per stream (multirate/rational_resampler.h:121-167) with the plan and taps of
+ * sdrgpu_rational_resampler_create: power decimator bank and / or polyphase resampler bank, or a copy;
+ * bit-identical to those banks run one after another. An interpolating plan writes more rows than it reads:
+ * size `out` by sdrgpu_bank_out_rows. */
+int sdrgpu_bank_rational_resampler_create(sdrgpu_bank** h, int device, int streams, int dtype, double inSamplerate,
+                                          double outSamplerate);
+
 /* device buffers of frames * S (in) and sdrgpu_bank_out_rows(frames) * S (out) elements, on `stream` (0:
  * the handle's own); asynchronous except for a bank that ends in MM (above). Returns the rows written. */
 int sdrgpu_bank_process_dev(sdrgpu_bank* h, const void* in, int frames, void* out, void* stream);
 int sdrgpu_bank_process(sdrgpu_bank* h, const void* in, int frames, void* out);   /* host buffers (synchronous) */
-int sdrgpu_bank_out_rows(sdrgpu_bank* h, int frames);     /* row capacity of the next call of `frames` rows */
+/* the rows the next call of `frames` rows writes, from the handle's current phase and offset (which it does not
+ * advance): exact for every bank but one that ends in MM, where it is the capacity (frames) */
+int sdrgpu_bank_out_rows(sdrgpu_bank* h, int frames);
 int sdrgpu_bank_out_counts(sdrgpu_bank* h, int* counts);  /* counts[S]: per-stream outputs of the last call (synchronises) */
 int sdrgpu_bank_streams(sdrgpu_bank* h);
 int sdrgpu_bank_reset(sdrgpu_bank* h);

@@ -190,6 +190,10 @@ def _load():
         "sdrgpu_bank_xlator_set_offset": (i, [vp, d]),
         "sdrgpu_bank_ssb_create": (i, [pp, i, i, i, d, d, i, d, d]),
         "sdrgpu_bank_cw_create": (i, [pp, i, i, d, i, d, d, d]),
+        "sdrgpu_bank_decimating_fir_create": (i, [pp, i, i, i, fp, i, i]),
+        "sdrgpu_bank_polyphase_resampler_create": (i, [pp, i, i, i, i, i, fp, i]),
+        "sdrgpu_bank_power_decimator_create": (i, [pp, i, i, i, i]),
+        "sdrgpu_bank_rational_resampler_create": (i, [pp, i, i, i, d, d]),
         "sdrgpu_bank_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_bank_process": (i, [vp, vp, i, vp]),
         "sdrgpu_bank_out_rows": (i, [vp, i]),

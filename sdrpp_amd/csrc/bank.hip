@@ -6,9 +6,12 @@
 //   BankAgc, BankDcb, BankDeemp      loop::AGC<T>, correction::DCBlocker<T>, filter::Deemphasis<float> per stream
 //   BankSquelch, BankMag     noise_reduction::Squelch per stream; volk_32fc_magnitude_32f over the flat stream
 //   BankXlator               channel::FrequencyXlator per stream on the single-stream NCO; also as translate -> real part
+//   BankRate, BankCopy       multirate::PolyphaseResampler<T> / filter::DecimatingFIR<D, float> per stream
+//                            (bank_rate_kernels.h); the copy of a ratio of 1
 //   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip),
 //                            demod::FM<float> / demod::AM<float> / demod::SSB<float> / demod::CW<float> per stream
-//                            (those of blocks.hip / loops.hip)
+//                            (those of blocks.hip / loops.hip),
+//                            multirate::PowerDecimator<T> / multirate::RationalResampler<T> per stream
 // Top to bottom: the Bank base and its handle, the blocks (each: configure = the argument checks and the
 // parameters, host only; init = device state; reset; run = its launch), the C entry points.
 // A create function checks every argument (configure, of a chain: of all its stages) before it selects
@@ -23,6 +26,7 @@
 #include "sdrgpu_internal.h"
 #include "bank_kernels.h"
 #include "bank_audio_kernels.h"
+#include "bank_rate_kernels.h"
 #include "blocks.h"
 #include "symsync_args.h"
 
@@ -44,6 +48,9 @@ struct Bank {
     virtual int reset() = 0;
     // frames rows at `in` -> rows at `out`, asynchronous on s unless the block says otherwise; returns the rows
     virtual int run(const void* in, int frames, void* out, hipStream_t s) = 0;
+    // the rows the next run() of `frames` rows writes, from the state as it is (which stays): exact, except for
+    // data-dependent counts (MM), where it is the capacity. Past rows_limit(): some stage's rows do not fit the index.
+    virtual long long out_rows(int frames) const { return frames; }
     // data-dependent per-stream counts (MM): rows past a stream's count keep what `out` held
     virtual bool ragged() const { return false; }
     virtual void counts(int* c) const { std::fill(c, c + S, lastRows); }
@@ -53,9 +60,11 @@ struct Bank {
         if (streams < 1 || streams > INT_MAX / 64) { set_error("bank: %d streams outside [1, %d]", streams, INT_MAX / 64); return false; }
         return true;
     }
+    long long rows_limit() const { return INT_MAX / S; }
+    // rows in and rows out of a call
     bool frames_ok(int frames) const {
-        if (frames < 0 || (long long)frames * S > INT_MAX) {
-            set_error("bank: %d frames of %d streams do not fit the kernels' int index", frames, S);
+        if (frames < 0 || frames > rows_limit() || out_rows(frames) > rows_limit()) {
+            set_error("bank: %d frames of %d streams, or the rows they yield, do not fit the kernels' int index", frames, S);
             return false;
         }
         return true;
@@ -482,9 +491,130 @@ struct BankXlator : Bank {
     }
 };
 
+// ------------------------------------------- decimating FIR, polyphase resampler
+// multirate::PolyphaseResampler<T> per stream (polyphase_resampler.h:69-99), and with interp = 1
+// filter::DecimatingFIR<D, float> (decimating_fir.h:45-68): the host side of PolyBlock (blocks.hip) over rows.
+// offset and phase are the bank's, not a stream's: the streams share their parameters and start together.
+struct BankRate : Bank {
+    int interp = 1, decim = 1, tpp = 1, phase = 0, offset = 0;
+    int R = 0;   // output rows per tile of the tiled kernel at most (a call may take fewer: run); 0: the direct kernel
+    std::vector<float> taps;
+    DevBuf bankDev, hist[2];
+    int cur = 0;
+    // The form that runs where the tile fits. Measured at 1024 streams x 1024 rows; the other
+    // form: SDRGPU_TUNING=1 SDRGPU_BANK_RATE_TILED=0 | 1, read at creation.
+    static constexpr bool kTiledDefault = true;
+    // Output rows per tile: R rows read ceil((R - 1) decim / interp) + tpp work rows at most, which fit
+    // RATE_LDS where (R - 1) decim <= (RATE_LDS / (64 esize) - tpp) interp. 0: no tile (the direct kernel).
+    static int rate_tile_rows(int dtype, int ip, int dc, int tpp_) {
+        const long long room = RATE_LDS / (RATE_W * (long long)esize(dtype)) - tpp_;
+        if (room < 0) return 0;
+        const long long r = std::min<long long>(room * ip / dc + 1, RATE_RMAX);
+        return r < RATE_RMIN ? 0 : (int)r;
+    }
+    int configure(int streams, int dtype, int ip, int dc, const float* t, int ntaps) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype) || !t || ntaps < 1 || ip < 1 || dc < 1) {
+            set_error("bank resampler: dtype %d not F32 / C64, no taps (%d), or interp %d / decim %d below 1", dtype, ntaps, ip, dc);
+            return SDRGPU_EARG;
+        }
+        const long long per = ((long long)ntaps + ip - 1) / ip;
+        if ((per - 1) * streams > INT_MAX || per * ip > INT_MAX) {
+            set_error("bank resampler: %lld taps per phase of %d phases and %d streams beyond the int index", per, ip, streams);
+            return SDRGPU_EARG;
+        }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        interp = ip;
+        decim = dc;
+        tpp = (int)per;
+        taps.assign(t, t + ntaps);
+        bool tiled = kTiledDefault;
+        if (const char* e = tuning_env("SDRGPU_BANK_RATE_TILED")) tiled = atoi(e) != 0;
+        R = tiled ? rate_tile_rows(dtype, ip, dc, tpp) : 0;
+        return SDRGPU_OK;
+    }
+    int HS() const { return (tpp - 1) * S; }
+    int init() override {
+        // multirate/polyphase_bank.h:15-47: phases[P - 1 - (i % P)][i / P] = taps[i], zero-padded
+        std::vector<float> b((size_t)interp * tpp, 0.0f);
+        for (size_t i = 0; i < taps.size(); i++) b[(size_t)((interp - 1) - (int)(i % interp)) * tpp + i / interp] = taps[i];
+        SDRGPU_CHECK(upload(bankDev, b));
+        for (auto& h : hist) SDRGPU_CHECK(h.ensure(esize(in_dtype) * (size_t)std::max(HS(), 1)));
+        return reset();
+    }
+    int reset() override {
+        SDRGPU_HIP(hipMemset(hist[cur].p, 0, hist[cur].bytes));
+        phase = offset = 0;
+        return SDRGPU_OK;
+    }
+    // while (offset < frames) { out; phase += decim; offset += phase / interp; phase %= interp; }
+    long long out_rows(int frames) const override {
+        const long long pos = (long long)offset * interp + phase, lim = (long long)frames * interp;
+        return pos >= lim ? 0 : (lim - 1 - pos) / decim + 1;
+    }
+    template <typename DT>
+    void launch(const void* in, void* out, const RateArgs& a, hipStream_t s) {
+        if (R > 0) {
+            const int rowsMost = (int)(((long long)(a.R - 1) * decim + interp - 1) / interp) + tpp;
+            const dim3 grid((unsigned)((a.M + a.R - 1) / a.R) * a.chunks);
+            hipLaunchKernelGGL(bank_rate_tiled_kernel<DT>, grid, dim3(RATE_TW * RATE_W), sizeof(DT) * (size_t)rowsMost * RATE_W, s,
+                               hist[cur].as<DT>(), (const DT*)in, bankDev.as<float>(), (DT*)out, a);
+        } else {
+            hipLaunchKernelGGL(bank_rate_direct_kernel<DT>, dim3((unsigned)a.M * a.chunks), dim3(RATE_XS), 0, s, hist[cur].as<DT>(),
+                               (const DT*)in, bankDev.as<float>(), (DT*)out, a);
+        }
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int M = (int)out_rows(frames);
+        const long long pos0 = (long long)offset * interp + phase;
+        if (M > 0) {
+            RateArgs a{};
+            a.S = S; a.H = tpp - 1; a.tpp = tpp; a.interp = interp;
+            a.qD = decim / interp; a.rD = decim % interp;
+            a.off0 = offset; a.ph0 = phase;
+            a.M = M;
+            a.chunks = R > 0 ? (S + RATE_W - 1) / RATE_W : (S + RATE_XS - 1) / RATE_XS;
+            // a short call gets smaller tiles, RATE_WGS workgroups where the rows allow, a row per wave at least
+            a.R = R > 0 ? std::min<long long>(R, std::max<long long>(RATE_TW, ((long long)M * a.chunks + RATE_WGS - 1) / RATE_WGS)) : 0;
+            if (in_dtype == SDRGPU_C64) launch<float2>(in, out, a, s);
+            else launch<float>(in, out, a, s);
+            SDRGPU_HIP(hipGetLastError());
+        }
+        if (HS() > 0) {
+            SDRGPU_CHECK(carry_history(in_dtype, nullptr, hist[cur], in, hist[cur ^ 1], HS(), frames * S, s));
+            cur ^= 1;
+        }
+        const long long pos = pos0 + (long long)M * decim;
+        offset = (int)(pos / interp - frames);
+        phase = (int)(pos % interp);
+        return M;
+    }
+};
+
+// the rows as they are: PowerDecimator with a ratio of 1 (power_decimator.h:52-56), RationalResampler's mode 3
+struct BankCopy : Bank {
+    int configure(int streams, int dtype) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype)) { set_error("bank copy: dtype %d not F32 / C64", dtype); return SDRGPU_EARG; }
+        S = streams;
+        in_dtype = out_dtype = dtype;
+        return SDRGPU_OK;
+    }
+    int init() override { return SDRGPU_OK; }
+    int reset() override { return SDRGPU_OK; }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        SDRGPU_HIP(hipMemcpyAsync(out, in, (size_t)frames * S * esize(in_dtype), hipMemcpyDeviceToDevice, s));
+        return frames;
+    }
+};
+
 // ------------------------------------------------- composites: stages back to back
-// Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers of
-// frames * S elements (sized for C64), which grow on demand.
+// Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers (sized
+// for C64) of the largest row count that a stage but the last writes (a resampler may write more rows than
+// it reads), which grow on demand.
 struct BankChain : Bank {
     std::vector<std::unique_ptr<Bank>> kids;
     DevBuf buf[2];
@@ -508,9 +638,24 @@ struct BankChain : Bank {
     }
     bool ragged() const override { return kids.back()->ragged(); }
     void counts(int* c) const override { kids.back()->counts(c); }
+    // the rows of the last stage; *most (if given): the largest count a stage before it writes. A stage's
+    // count past the index limit ends the walk: the limit + 1 is returned (frames_ok refuses it).
+    long long walk_rows(int frames, long long* most) const {
+        long long rows = frames, m = 0;
+        for (size_t i = 0; i < kids.size(); i++) {
+            rows = kids[i]->out_rows((int)rows);
+            if (rows > rows_limit()) return rows_limit() + 1;
+            if (i + 1 < kids.size()) m = std::max(m, rows);
+        }
+        if (most) *most = m;
+        return rows;
+    }
+    long long out_rows(int frames) const override { return walk_rows(frames, nullptr); }
     int run(const void* in, int frames, void* out, hipStream_t s) override {
+        long long most = 0;
+        (void)walk_rows(frames, &most);
         if (kids.size() > 1)
-            for (auto& b : buf) SDRGPU_CHECK(b.ensure((size_t)std::max(frames, 1) * S * esize(SDRGPU_C64)));
+            for (auto& b : buf) SDRGPU_CHECK(b.ensure((size_t)std::max<long long>(most, 1) * S * esize(SDRGPU_C64)));
         const void* cur = in;
         int rows = frames;
         for (size_t i = 0; i < kids.size(); i++) {
@@ -798,6 +943,72 @@ extern "C" int sdrgpu_bank_cw_create(sdrgpu_bank** h, int device, int streams, d
                              1.0);
 }
 
+// -- rate-changing banks
+// filter::DecimatingFIR<D, float> per stream (decimating_fir.h:45-68): the resampler bank with one phase
+extern "C" int sdrgpu_bank_decimating_fir_create(sdrgpu_bank** h, int device, int streams, int dtype, const float* taps, int ntaps,
+                                                 int decim) {
+    NEED_BANK_OUT(h, "bank_decimating_fir_create");
+    auto* r = new BankRate();
+    return publish_bank(h, r, device, r->configure(streams, dtype, 1, decim, taps, ntaps));
+}
+// multirate::PolyphaseResampler<T> per stream (polyphase_resampler.h:69-99)
+extern "C" int sdrgpu_bank_polyphase_resampler_create(sdrgpu_bank** h, int device, int streams, int dtype, int interp, int decim,
+                                                      const float* taps, int ntaps) {
+    NEED_BANK_OUT(h, "bank_polyphase_resampler_create");
+    auto* r = new BankRate();
+    return publish_bank(h, r, device, r->configure(streams, dtype, interp, decim, taps, ntaps));
+}
+
+// a chain of one element type; rc: the status of the checks so far
+static BankChain* new_rate_chain(int streams, int dtype, int& rc) {
+    auto* c = new BankChain();
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    else if (!real_or_complex(dtype)) { set_error("bank resampler: dtype %d not F32 / C64", dtype); rc = SDRGPU_EARG; }
+    c->S = std::max(streams, 1);
+    c->in_dtype = c->out_dtype = dtype;
+    return c;
+}
+static int add_copy(BankChain* c, int streams, int dtype) {
+    auto* b = new BankCopy();
+    return c->add(b, b->configure(streams, dtype));
+}
+// multirate::PowerDecimator<T> (power_decimator.h:51-108): the stages of the plan, one decimating FIR bank each
+static int add_power_decim(BankChain* c, int streams, int dtype, int ratio) {
+    if (ratio == 1) return add_copy(c, streams, dtype);
+    int d[8], n[8];
+    const float* t[8];
+    const int ns = decim_plan(ratio, d, n, t);
+    if (ns < 0) return ns;
+    for (int i = 0; i < ns; i++) {
+        auto* r = new BankRate();
+        SDRGPU_CHECK(c->add(r, r->configure(streams, dtype, 1, d[i], t[i], n[i])));
+    }
+    return SDRGPU_OK;
+}
+extern "C" int sdrgpu_bank_power_decimator_create(sdrgpu_bank** h, int device, int streams, int dtype, int ratio) {
+    NEED_BANK_OUT(h, "bank_power_decimator_create");
+    int rc = SDRGPU_OK;
+    auto* c = new_rate_chain(streams, dtype, rc);
+    if (rc >= 0) rc = add_power_decim(c, streams, dtype, ratio);
+    return publish_bank(h, c, device, rc);
+}
+// multirate::RationalResampler<T> (rational_resampler.h:121-167): the plan of sdrgpu_rational_resampler_create
+extern "C" int sdrgpu_bank_rational_resampler_create(sdrgpu_bank** h, int device, int streams, int dtype, double inSamplerate,
+                                                     double outSamplerate) {
+    NEED_BANK_OUT(h, "bank_rational_resampler_create");
+    int rc = SDRGPU_OK;
+    auto* c = new_rate_chain(streams, dtype, rc);
+    RationalPlan rp;
+    if (rc >= 0) rc = plan_rational(inSamplerate, outSamplerate, rp);
+    if (rc >= 0 && (rp.mode == 0 || rp.mode == 1)) rc = add_power_decim(c, streams, dtype, rp.predec);
+    if (rc >= 0 && (rp.mode == 0 || rp.mode == 2)) {
+        auto* r = new BankRate();
+        rc = c->add(r, r->configure(streams, dtype, rp.interp, rp.decim, rp.taps.data(), (int)rp.taps.size()));
+    }
+    if (rc >= 0 && rp.mode == 3) rc = add_copy(c, streams, dtype);
+    return publish_bank(h, c, device, rc);
+}
+
 extern "C" int sdrgpu_bank_streams(sdrgpu_bank* h) {
     NEED_BANK(h);
     return h->impl->S;
@@ -805,7 +1016,7 @@ extern "C" int sdrgpu_bank_streams(sdrgpu_bank* h) {
 
 extern "C" int sdrgpu_bank_out_rows(sdrgpu_bank* h, int frames) {
     NEED_BANK(h);
-    return h->impl->frames_ok(frames) ? frames : SDRGPU_EARG;
+    return h->impl->frames_ok(frames) ? (int)h->impl->out_rows(frames) : SDRGPU_EARG;
 }
 
 extern "C" int sdrgpu_bank_process_dev(sdrgpu_bank* h, const void* in, int frames, void* out, void* stream) {
@@ -830,7 +1041,8 @@ extern "C" int sdrgpu_bank_process(sdrgpu_bank* h, const void* in, int frames, v
     if (!b->frames_ok(frames)) return SDRGPU_EARG;
     if (frames > 0 && (!in || !out)) { set_error("bank_process: bad buffers"); return SDRGPU_EARG; }
     SDRGPU_SET_DEVICE(b->device);
-    const size_t inB = (size_t)frames * b->S * esize(b->in_dtype), outB = (size_t)frames * b->S * esize(b->out_dtype);
+    const size_t inB = (size_t)frames * b->S * esize(b->in_dtype);
+    const size_t outB = (size_t)b->out_rows(frames) * b->S * esize(b->out_dtype);   // (a resampler may write more rows than it reads)
     SDRGPU_CHECK(b->pin_in.ensure(std::max<size_t>(inB, 1)));
     SDRGPU_CHECK(b->pin_out.ensure(std::max<size_t>(outB, 1)));
     SDRGPU_CHECK(b->dev_in.ensure(std::max<size_t>(inB, 1)));

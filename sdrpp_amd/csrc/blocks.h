@@ -1,7 +1,7 @@
 // What the other translation units call in blocks.hip (host side only): chains of blocks and the
 // block constructors (loops.hip, symsync.hip), the gate and the publication of a handle (with the rules of who
 // selects the device, owns a stream and waits) and the history carry (loops.hip, channelizer.hip, ifnr.hip,
-// symsync.hip), and the hooks through which a spectrum launch carries an RxVFO's stages (fft.hip, frontend.hip).
+// symsync.hip), the xlator's NCO and the rational resampler's plan (bank.hip), and the hooks through which a spectrum launch carries an RxVFO's stages (fft.hip, frontend.hip).
 #pragma once
 #include "sdrgpu_internal.h"
 
@@ -94,6 +94,16 @@ void nco_reset(Nco* n);
 // FrequencyXlator::setOffset (frequency_xlator.h:25-29) of an xlator block (make_xlator_block): the phase is kept;
 // SDRGPU_ESTATE on another block. The caller has waited for the device: a queued call still reads the table.
 int xlator_block_set_offset(Block* xlator, double offsetRad);
+
+// ---- the rational resampler's plan for a resampler outside blocks.hip (bank.hip) -----------------
+// RationalResampler<T>::reconfigure (multirate/rational_resampler.h:121-167), host only: mode 0 = PowerDecimator
+// (predec) then PolyphaseResampler(interp, decim, taps), 1 = the decimator alone, 2 = the resampler alone, 3 = a
+// copy; taps = lowPass(min(in, out) / 2, 10 %, intSr * interp) * interp. Sample rates not > 0: SDRGPU_EARG.
+struct RationalPlan {
+    int mode = 3, predec = 1, interp = 1, decim = 1;
+    std::vector<float> taps;
+};
+int plan_rational(double inSr, double outSr, RationalPlan& rp);
 
 // ---- an RxVFO inside the spectrum launches ------------------------------------------------------
 struct VfoStage1;   // fir_rows.h

@@ -909,12 +909,8 @@ static int build_power_decim(ChainBlock* c, int dev, int dtype, int ratio, bool 
     return SDRGPU_OK;
 }
 
-// RationalResampler<T>::reconfigure (multirate/rational_resampler.h:121-167)
-struct RationalPlan {
-    int mode = 3, predec = 1, interp = 1, decim = 1;
-    std::vector<float> taps;
-};
-static int plan_rational(double inSr, double outSr, RationalPlan& rp) {
+// RationalResampler<T>::reconfigure (multirate/rational_resampler.h:121-167); RationalPlan: blocks.h
+int plan_rational(double inSr, double outSr, RationalPlan& rp) {
     if (!(inSr > 0) || !(outSr > 0)) { set_error("rational resampler: bad samplerates"); return SDRGPU_EARG; }
     const int maxRatio = 8192;
     int predecPower = std::min<int>((int)std::floor(std::log2(inSr / outSr)), maxRatio);

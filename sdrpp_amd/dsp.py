@@ -851,6 +851,48 @@ class BankCW(_XlateAgcBank):
         super().__init__(h, np.complex64, np.float32)
 
 
+class _RateBank(Bank):
+    """A bank that writes another number of rows than it reads: ``out_rows(frames)`` is the exact count of
+    the next call, ``counts`` is that count for every stream."""
+
+    def __init__(self, fn, streams, complex_data, device, *args):
+        npd = np.complex64 if complex_data else np.float32
+        super().__init__(_make(fn, device, int(streams), C64 if complex_data else F32, *args), npd, npd)
+
+
+class BankDecimatingFIR(_RateBank):
+    """dsp::filter::DecimatingFIR<D, float> per stream: real taps shared by all streams."""
+
+    def __init__(self, streams, taps, decim, complex_data=True, device=0):
+        t = np.ascontiguousarray(taps, np.float32)
+        self._taps = t
+        super().__init__(lib.sdrgpu_bank_decimating_fir_create, streams, complex_data, device, _fptr(t), int(t.shape[0]), int(decim))
+
+
+class BankPolyphaseResampler(_RateBank):
+    """dsp::multirate::PolyphaseResampler<T> per stream; arguments as PolyphaseResampler."""
+
+    def __init__(self, streams, interp, decim, taps, complex_data=True, device=0):
+        t = np.ascontiguousarray(taps, np.float32)
+        self._taps = t
+        super().__init__(lib.sdrgpu_bank_polyphase_resampler_create, streams, complex_data, device, int(interp), int(decim),
+                         _fptr(t), int(t.shape[0]))
+
+
+class BankPowerDecimator(_RateBank):
+    """dsp::multirate::PowerDecimator<T> per stream: the stages of decim_plan(ratio); ratio 1 copies."""
+
+    def __init__(self, streams, ratio, complex_data=True, device=0):
+        super().__init__(lib.sdrgpu_bank_power_decimator_create, streams, complex_data, device, int(ratio))
+
+
+class BankRationalResampler(_RateBank):
+    """dsp::multirate::RationalResampler<T> per stream; the plan and taps of RationalResampler."""
+
+    def __init__(self, streams, in_sr, out_sr, complex_data=True, device=0):
+        super().__init__(lib.sdrgpu_bank_rational_resampler_create, streams, complex_data, device, float(in_sr), float(out_sr))
+
+
 class DCBlocker(Block):
     """dsp::correction::DCBlocker<T> (correction/dc_blocker.h); rate in 1/sample."""
 
