@@ -478,6 +478,36 @@ int sdrgpu_bank_power_decimator_create(sdrgpu_bank** h, int device, int streams,
 int sdrgpu_bank_rational_resampler_create(sdrgpu_bank** h, int device, int streams, int dtype, double inSamplerate,
                                           double outSamplerate);
 
+/* -- broadcast FM banks: stereo_t is C64 with (l, r) = (re, im); rows out = rows in; every call is
+ * asynchronous on its stream; a call of 0 frames changes nothing. No RDS branch, no setters. */
+/* filter::FIR<complex_t, complex_t> per stream (filter/fir.h:75, volk_32fc_x2_dot_prod_32fc): `taps` is ntaps (re, im)
+ * pairs shared by all streams, not reversed; out[m*S + k] = sum_t buf_k[m + t] * taps[t] over [ntaps - 1 history
+ * rows || new], per tap re += (x.re*t.re) - (x.im*t.im), im += (x.re*t.im) + (x.im*t.re), in ascending tap order in
+ * fp32 without contraction, so the result does not depend on how the rows are cut into calls. Output C64. in_dtype
+ * C64: the block itself; F32: convert::RealToComplex first (demod/broadcast_fm.h:149-152) in the same launch,
+ * bit-identical to C64 input with zero imaginary parts (finite taps). History zero at create / reset. in_dtype not
+ * F32 / C64, null taps, ntaps < 1, or (ntaps - 1) * streams beyond INT_MAX: SDRGPU_EARG */
+int sdrgpu_bank_fir_complex_create(sdrgpu_bank** h, int device, int streams, int in_dtype, const float* taps, int ntaps);
+/* The stereo decoder of demod::BroadcastFM per stream (demod/broadcast_fm.h:147-162, 173-190; loop/pll.h:64-70), F32 MPX
+ * -> C64 (l, r), with the constants of sdrgpu_broadcast_fm_create: pilot filter = the complex-tap FIR bank with
+ * bandPass<complex_t>(18750, 19250, 3000, samplerate, odd) on the real MPX, PLL(25000 / samplerate, 0, 19 kHz, 18.75 kHz,
+ * 19.25 kHz) one lane per stream on the single-stream block's step, delay ((np - 1) / 2) + 1 rows, then its matrix
+ * expression. reset: the filter and delay histories to zero, (phase, freq) to (0, 19 kHz) (:129-141). Not bit-identical to
+ * the single-stream block, whose pilot filter sums in another order. samplerate not > 0, or pilot taps * streams beyond
+ * INT_MAX: SDRGPU_EARG */
+int sdrgpu_bank_stereo_decoder_create(sdrgpu_bank** h, int device, int streams, double samplerate);
+/* demod::BroadcastFM per stream (demod/broadcast_fm.h:34-60, 144-215), C64 -> C64 (l, r); arguments in the order of
+ * sdrgpu_broadcast_fm_create. stereo: bank quadrature(hzToRads(deviation, samplerate)) -> stereo decoder bank ->
+ * [lowPass: sdrgpu_bank_fir_create(C64, lowPass(15000, 4000, samplerate))]; mono: bank quadrature -> [lowPass: the same
+ * taps, F32] -> (l, r) = (x, x) (:211). Bit-identical to those banks run one after another. samplerate or deviation not
+ * > 0, or a samplerate at which the audio low-pass has no taps (as sdrgpu_broadcast_fm_create, with lowPass or
+ * without): SDRGPU_EARG */
+int sdrgpu_bank_broadcast_fm_create(sdrgpu_bank** h, int device, int streams, double deviation, double samplerate, int stereo,
+                                    int lowPass);
+/* filter::Deemphasis<stereo_t> per stream (filter/deephasis.h:66-76, 91-94): C64 rows of (l, r), each channel
+ * bit-identical to sdrgpu_deemphasis_create(SDRGPU_C64 as stereo_t) fed that column; samplerate not > 0: SDRGPU_EARG */
+int sdrgpu_bank_deemphasis_stereo_create(sdrgpu_bank** h, int device, int streams, double tau, double samplerate);
+
 /* device buffers of frames * S (in) and sdrgpu_bank_out_rows(frames) * S (out) elements, on `stream` (0:
  * the handle's own); asynchronous except for a bank that ends in MM (above). Returns the rows written. */
 int sdrgpu_bank_process_dev(sdrgpu_bank* h, const void* in, int frames, void* out, void* stream);

@@ -194,6 +194,10 @@ def _load():
         "sdrgpu_bank_polyphase_resampler_create": (i, [pp, i, i, i, i, i, fp, i]),
         "sdrgpu_bank_power_decimator_create": (i, [pp, i, i, i, i]),
         "sdrgpu_bank_rational_resampler_create": (i, [pp, i, i, i, d, d]),
+        "sdrgpu_bank_fir_complex_create": (i, [pp, i, i, i, fp, i]),
+        "sdrgpu_bank_stereo_decoder_create": (i, [pp, i, i, d]),
+        "sdrgpu_bank_broadcast_fm_create": (i, [pp, i, i, d, d, i, i]),
+        "sdrgpu_bank_deemphasis_stereo_create": (i, [pp, i, i, d, d]),
         "sdrgpu_bank_process_dev": (i, [vp, vp, i, vp, vp]),
         "sdrgpu_bank_process": (i, [vp, vp, i, vp]),
         "sdrgpu_bank_out_rows": (i, [vp, i]),

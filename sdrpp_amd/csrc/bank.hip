@@ -8,9 +8,11 @@
 //   BankXlator               channel::FrequencyXlator per stream on the single-stream NCO; also as translate -> real part
 //   BankRate, BankCopy       multirate::PolyphaseResampler<T> / filter::DecimatingFIR<D, float> per stream
 //                            (bank_rate_kernels.h); the copy of a ratio of 1
+//   BankCfir, BankStereoDec, BankMonoPairs   filter::FIR<complex_t, complex_t> per stream; the stereo decoder of
+//                            demod::BroadcastFM (pilot filter -> PLL -> matrix) and its mono -> pairs (bank_wfm_kernels.h)
 //   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip),
 //                            demod::FM<float> / demod::AM<float> / demod::SSB<float> / demod::CW<float> per stream
-//                            (those of blocks.hip / loops.hip),
+//                            (those of blocks.hip / loops.hip), demod::BroadcastFM per stream (those of loops.hip),
 //                            multirate::PowerDecimator<T> / multirate::RationalResampler<T> per stream
 // Top to bottom: the Bank base and its handle, the blocks (each: configure = the argument checks and the
 // parameters, host only; init = device state; reset; run = its launch), the C entry points.
@@ -27,6 +29,7 @@
 #include "bank_kernels.h"
 #include "bank_audio_kernels.h"
 #include "bank_rate_kernels.h"
+#include "bank_wfm_kernels.h"
 #include "blocks.h"
 #include "symsync_args.h"
 
@@ -375,24 +378,31 @@ struct BankDcb : Bank {
 };
 
 // ------------------------------------------------------------------ Deemphasis
+// filter::Deemphasis<float> (channels = 1) or <stereo_t> (2: C64 rows of (l, r)) per stream
 struct BankDeemp : Bank {
     float alpha = 1.0f;
-    DevBuf state;   // lastOut[S]
-    int configure(int streams, double tau, double samplerate) {
+    int channels = 1;
+    DevBuf state;   // lastOut[S]; stereo: l[S], r[S]
+    int configure(int streams, double tau, double samplerate, bool stereo) {
         if (!streams_ok(streams)) return SDRGPU_EARG;
         if (!(samplerate > 0)) { set_error("bank_deemphasis: samplerate %g not positive", samplerate); return SDRGPU_EARG; }
         S = streams;
-        in_dtype = out_dtype = SDRGPU_F32;
+        channels = stereo ? 2 : 1;
+        in_dtype = out_dtype = stereo ? SDRGPU_C64 : SDRGPU_F32;
         const float dt = (float)(1.0f / samplerate);   // updateAlpha (deephasis.h:91-94), as sdrgpu_deemphasis_create
         alpha = (float)((double)dt / (tau + (double)dt));
         return SDRGPU_OK;
     }
     int init() override { return reset(); }
-    int reset() override { return upload(state, std::vector<float>(S, 0.0f)); }
+    int reset() override { return upload(state, std::vector<float>((size_t)channels * S, 0.0f)); }
     int run(const void* in, int frames, void* out, hipStream_t s) override {
         if (frames == 0) return 0;
-        hipLaunchKernelGGL(bank_deemp_kernel, waves_of(S), dim3(BANK_W), 0, s, (const float*)in, (float*)out, frames, S, alpha,
-                           state.as<float>());
+        if (channels == 2)
+            hipLaunchKernelGGL((bank_deemp_kernel<2, float2>), waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S,
+                               alpha, state.as<float>());
+        else
+            hipLaunchKernelGGL((bank_deemp_kernel<1, float>), waves_of(S), dim3(BANK_W), 0, s, (const float*)in, (float*)out, frames, S,
+                               alpha, state.as<float>());
         SDRGPU_HIP(hipGetLastError());
         return frames;
     }
@@ -611,6 +621,177 @@ struct BankCopy : Bank {
     }
 };
 
+// ------------------------------------------------------- complex-tap FIR
+// filter::FIR<complex_t, complex_t> per stream (fir.h:75): (re, im) tap pairs shared by all streams, F32
+// (convert::RealToComplex first, in the same launch) or C64 in, C64 out; `phase`: atan2f of the output
+// instead (F32), the stereo decoder's first launch. The kernels and their two forms: bank_wfm_kernels.h.
+struct BankCfir : Bank {
+    std::vector<float2> taps;
+    DevBuf tapsDev, hist[2];
+    int cur = 0;
+    bool tiled = true, phase = false;
+    // The form that runs from CFIR_RMIN rows on. Measured at 1024 streams x 1024 rows, 305 taps;
+    // the other form: SDRGPU_TUNING=1 SDRGPU_BANK_CFIR_TILED=0 | 1, read at creation.
+    static constexpr bool kTiledDefault = true;
+    int configure(int streams, int dtype, const float* t, int ntaps, bool phaseOut) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!real_or_complex(dtype) || !t || ntaps < 1 || (long long)(ntaps - 1) * streams > INT_MAX) {
+            set_error("bank_fir_complex: dtype %d not F32 / C64, no taps, or %d taps of %d streams beyond the int index", dtype, ntaps,
+                      streams);
+            return SDRGPU_EARG;
+        }
+        S = streams;
+        in_dtype = dtype;
+        out_dtype = phaseOut ? SDRGPU_F32 : SDRGPU_C64;
+        phase = phaseOut;
+        taps.resize(ntaps);
+        for (int i = 0; i < ntaps; i++) taps[i] = make_float2(t[2 * i], t[2 * i + 1]);
+        tiled = kTiledDefault;
+        if (const char* e = tuning_env("SDRGPU_BANK_CFIR_TILED")) tiled = atoi(e) != 0;
+        return SDRGPU_OK;
+    }
+    int T() const { return (int)taps.size(); }
+    int HS() const { return (T() - 1) * S; }
+    int init() override {
+        SDRGPU_CHECK(upload(tapsDev, taps));
+        for (auto& b : hist) SDRGPU_CHECK(b.ensure(esize(in_dtype) * (size_t)std::max(HS(), 1)));
+        return reset();
+    }
+    int reset() override {
+        SDRGPU_HIP(hipMemset(hist[cur].p, 0, hist[cur].bytes));
+        return SDRGPU_OK;
+    }
+    // The tile of a call of M rows: R rows, as many as give CFIR_WGS workgroups, a row per wave at least and
+    // CFIR_RPW at most; the taps in the fewest equal segments whose R + Tc - 1 staged rows fit CFIR_LDS.
+    void cfir_tile(CfirArgs& a) const {
+        a.chunks = (S + CFIR_W - 1) / CFIR_W;
+        a.R = (int)std::min<long long>(CFIR_TW * CFIR_RPW, std::max<long long>(CFIR_TW, ((long long)a.M * a.chunks + CFIR_WGS - 1) / CFIR_WGS));
+        const int most = CFIR_LDS / (CFIR_W * (int)esize(in_dtype)) - a.R + 1;   // >= 65 taps
+        const int segs = (a.T + most - 1) / most;
+        a.Tc = (a.T + segs - 1) / segs;
+    }
+    template <typename IN, bool PHASE>
+    void launch(const void* in, void* out, CfirArgs& a, hipStream_t s) {
+        if (tiled && a.M >= CFIR_RMIN) {
+            cfir_tile(a);
+            const dim3 grid((unsigned)((a.M + a.R - 1) / a.R) * a.chunks);
+            hipLaunchKernelGGL((bank_cfir_tiled_kernel<IN, PHASE>), grid, dim3(CFIR_TW * CFIR_W), sizeof(IN) * (size_t)(a.R + a.Tc - 1) * CFIR_W,
+                               s, hist[cur].as<IN>(), (const IN*)in, tapsDev.as<float2>(), out, a);
+        } else {
+            a.chunks = (S + CFIR_XS - 1) / CFIR_XS;
+            hipLaunchKernelGGL((bank_cfir_direct_kernel<IN, PHASE>), dim3((unsigned)a.M * a.chunks), dim3(CFIR_XS), 0, s, hist[cur].as<IN>(),
+                               (const IN*)in, tapsDev.as<float2>(), out, a);
+        }
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        CfirArgs a{};
+        a.S = S; a.H = T() - 1; a.T = T(); a.M = frames;
+        if (in_dtype == SDRGPU_C64) {
+            if (phase) launch<float2, true>(in, out, a, s);
+            else launch<float2, false>(in, out, a, s);
+        } else {
+            if (phase) launch<float, true>(in, out, a, s);
+            else launch<float, false>(in, out, a, s);
+        }
+        SDRGPU_HIP(hipGetLastError());
+        if (HS() > 0) {
+            SDRGPU_CHECK(carry_history(in_dtype, nullptr, hist[cur], in, hist[cur ^ 1], HS(), frames * S, s));
+            cur ^= 1;
+        }
+        return frames;
+    }
+};
+
+// ------------------------------------------------------------- stereo decoder
+// The part of BroadcastFM::process between the quadrature and the audio filters (broadcast_fm.h:147-162, 173-190)
+// per stream, with the constants of BroadcastFmBlock::setup (loops.hip): F32 MPX -> C64 (l, r). Three launches:
+// the pilot filter on the real MPX writing the pilot's phase, the PLL walk in place on that plane, the matrix.
+struct BankStereoDec : Bank {
+    BankCfir pilot;
+    PllParams pp{};
+    float initFreq = 0.0f;
+    int delay = 0;             // lprDelay / lmrDelay: the pilot filter's group delay, in rows
+    DevBuf pll, hist[2], ph;   // phase[S], freq[S]; the delay line's last `delay` MPX rows, ping-pong; a call's phase plane
+    int cur = 0;
+    int configure(int streams, double samplerate) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        if (!(samplerate > 0)) { set_error("bank_stereo_decoder: samplerate %g not positive", samplerate); return SDRGPU_EARG; }
+        const int np = taps_band_pass_c(18750.0, 19250.0, 3000.0, samplerate, 1, nullptr);
+        if (np < 1) return np < 0 ? np : SDRGPU_EARG;
+        if ((long long)(np - 1) * streams > INT_MAX) {
+            set_error("bank_stereo_decoder: %d pilot taps of %d streams beyond the int index", np, streams);
+            return SDRGPU_EARG;
+        }
+        std::vector<float> pt(2 * (size_t)np);
+        taps_band_pass_c(18750.0, 19250.0, 3000.0, samplerate, 1, pt.data());
+        SDRGPU_CHECK(pilot.configure(streams, SDRGPU_F32, pt.data(), np, true));
+        S = streams;
+        in_dtype = SDRGPU_F32;
+        out_dtype = SDRGPU_C64;
+        delay = ((np - 1) / 2) + 1;
+        // PLL(25000 / fs, 0, 19 kHz, 18.75 kHz, 19.25 kHz) (broadcast_fm.h:47)
+        critically_damped(25000.0 / samplerate, &pp.alpha, &pp.beta);
+        pp.minPhase = -3.1415926535f;
+        pp.maxPhase = 3.1415926535f;
+        pp.phaseDelta = pp.maxPhase - pp.minPhase;
+        pp.minFreq = (float)hz_to_rads(18750.0, samplerate);
+        pp.maxFreq = (float)hz_to_rads(19250.0, samplerate);
+        initFreq = (float)hz_to_rads(19000.0, samplerate);
+        return SDRGPU_OK;
+    }
+    int DS() const { return delay * S; }   // (delay <= the pilot's history rows, whose product with S fits)
+    int init() override {
+        pilot.device = device;
+        SDRGPU_CHECK(pilot.init());
+        for (auto& b : hist) SDRGPU_CHECK(b.ensure(sizeof(float) * (size_t)DS()));
+        return reset_own();
+    }
+    int reset_own() {   // broadcast_fm.h:129-141: the delay lines; the PLL back to (0, 19 kHz)
+        SDRGPU_HIP(hipMemset(hist[cur].p, 0, hist[cur].bytes));
+        std::vector<float> st(2 * (size_t)S, 0.0f);
+        std::fill(st.begin() + S, st.end(), initFreq);
+        return upload(pll, st);
+    }
+    int reset() override {
+        SDRGPU_CHECK(pilot.reset());
+        return reset_own();
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int n = frames * S;
+        SDRGPU_CHECK(ph.ensure(sizeof(float) * (size_t)n));
+        SDRGPU_CHECK(pilot.run(in, frames, ph.p, s));
+        hipLaunchKernelGGL(bank_pll_kernel, waves_of(S), dim3(BANK_W), 0, s, ph.as<float>(), frames, S, pp, pll.as<float>());
+        hipLaunchKernelGGL(bank_stereo_matrix_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)in, hist[cur].as<float>(), DS(),
+                           ph.as<float>(), (float2*)out, n);
+        SDRGPU_HIP(hipGetLastError());
+        SDRGPU_CHECK(carry_history(SDRGPU_F32, nullptr, hist[cur], in, hist[cur ^ 1], DS(), n, s));
+        cur ^= 1;
+        return frames;
+    }
+};
+
+// convert::MonoToStereo per stream (broadcast_fm.h:211): F32 -> C64 (l, r), l = r
+struct BankMonoPairs : Bank {
+    int configure(int streams) {
+        if (!streams_ok(streams)) return SDRGPU_EARG;
+        S = streams;
+        in_dtype = SDRGPU_F32;
+        out_dtype = SDRGPU_C64;
+        return SDRGPU_OK;
+    }
+    int init() override { return SDRGPU_OK; }
+    int reset() override { return SDRGPU_OK; }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        const int n = frames * S;
+        hipLaunchKernelGGL(bank_mono_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const float*)in, (float2*)out, n);
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
 // ------------------------------------------------- composites: stages back to back
 // Every stage runs on the caller's stream; the stages' rows go through two ping-pong buffers (sized
 // for C64) of the largest row count that a stage but the last writes (a resampler may write more rows than
@@ -803,7 +984,13 @@ extern "C" int sdrgpu_bank_dc_blocker_create(sdrgpu_bank** h, int device, int st
 extern "C" int sdrgpu_bank_deemphasis_create(sdrgpu_bank** h, int device, int streams, double tau, double samplerate) {
     NEED_BANK_OUT(h, "bank_deemphasis_create");
     auto* d = new BankDeemp();
-    return publish_bank(h, d, device, d->configure(streams, tau, samplerate));
+    return publish_bank(h, d, device, d->configure(streams, tau, samplerate, false));
+}
+// filter::Deemphasis<stereo_t> per stream (deephasis.h:67-77): C64 rows of (l, r)
+extern "C" int sdrgpu_bank_deemphasis_stereo_create(sdrgpu_bank** h, int device, int streams, double tau, double samplerate) {
+    NEED_BANK_OUT(h, "bank_deemphasis_stereo_create");
+    auto* d = new BankDeemp();
+    return publish_bank(h, d, device, d->configure(streams, tau, samplerate, true));
 }
 // noise_reduction::Squelch per stream (squelch.h:33-63)
 extern "C" int sdrgpu_bank_squelch_create(sdrgpu_bank** h, int device, int streams, double level) {
@@ -1006,6 +1193,41 @@ extern "C" int sdrgpu_bank_rational_resampler_create(sdrgpu_bank** h, int device
         rc = c->add(r, r->configure(streams, dtype, rp.interp, rp.decim, rp.taps.data(), (int)rp.taps.size()));
     }
     if (rc >= 0 && rp.mode == 3) rc = add_copy(c, streams, dtype);
+    return publish_bank(h, c, device, rc);
+}
+
+// -- broadcast FM
+// filter::FIR<complex_t, complex_t> per stream (fir.h:75); in_dtype F32: convert::RealToComplex first, in the same launch
+extern "C" int sdrgpu_bank_fir_complex_create(sdrgpu_bank** h, int device, int streams, int in_dtype, const float* taps, int ntaps) {
+    NEED_BANK_OUT(h, "bank_fir_complex_create");
+    auto* f = new BankCfir();
+    return publish_bank(h, f, device, f->configure(streams, in_dtype, taps, ntaps, false));
+}
+// the stereo decoder of demod::BroadcastFM per stream (broadcast_fm.h:147-162, 173-190): F32 MPX -> C64 (l, r)
+extern "C" int sdrgpu_bank_stereo_decoder_create(sdrgpu_bank** h, int device, int streams, double samplerate) {
+    NEED_BANK_OUT(h, "bank_stereo_decoder_create");
+    auto* d = new BankStereoDec();
+    return publish_bank(h, d, device, d->configure(streams, samplerate));
+}
+// demod::BroadcastFM per stream (broadcast_fm.h:34-60, 144-215): the stages and constants of sdrgpu_broadcast_fm_create
+// (loops.hip) without the RDS branch. As there, the audio low-pass is designed whether it runs or not: a
+// sample rate at which it has no taps is refused either way.
+extern "C" int sdrgpu_bank_broadcast_fm_create(sdrgpu_bank** h, int device, int streams, double deviation, double samplerate,
+                                               int stereo, int lowPass) {
+    NEED_BANK_OUT(h, "bank_broadcast_fm_create");
+    auto* c = new BankChain();
+    int rc = SDRGPU_OK;
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    else if (!(samplerate > 0) || !(deviation > 0)) { set_error("bank_broadcast_fm_create: samplerate and deviation must be positive"); rc = SDRGPU_EARG; }
+    c->S = std::max(streams, 1);
+    c->in_dtype = c->out_dtype = SDRGPU_C64;
+    std::vector<float> at;
+    if (rc >= 0) rc = design_taps(at, taps_low_pass, 15000.0, 4000.0, samplerate, 0);
+    if (rc >= 0) { auto* q = new BankQuad(); rc = c->add(q, q->configure(streams, hz_to_rads(deviation, samplerate))); }
+    if (rc >= 0 && stereo) { auto* d = new BankStereoDec(); rc = c->add(d, d->configure(streams, samplerate)); }
+    // alFir / arFir (broadcast_fm.h:205-208): the (l, r) pairs as one C64 stream through real taps; mono: the MPX
+    if (rc >= 0 && lowPass) { auto* f = new BankFir(); rc = c->add(f, f->configure(streams, stereo ? SDRGPU_C64 : SDRGPU_F32, at.data(), (int)at.size())); }
+    if (rc >= 0 && !stereo) { auto* m = new BankMonoPairs(); rc = c->add(m, m->configure(streams)); }
     return publish_bank(h, c, device, rc);
 }
 

@@ -4,7 +4,7 @@
 // Device code of bank.hip, the analogue receiver banks (the layout and the lane-per-stream walk are in
 // bank_kernels.h):
 //   loop::AGC<T>, correction::DCBlocker<T>,
-//   filter::Deemphasis<float>                  one lane per stream, on the steps of loop_steps.h
+//   filter::Deemphasis<float | stereo_t>       one lane per stream, on the steps of loop_steps.h
 //   noise_reduction::Squelch                   column sums in a fixed order, a lane-per-stream decision, a gate
 //   volk_32fc_magnitude_32f                    one thread per element of the flat frames * S stream
 //
@@ -105,16 +105,29 @@ __global__ __launch_bounds__(BANK_W) void bank_dcb_kernel(const DT* __restrict__
 }
 
 // ----------------------------------------------------------------- Deemphasis
-// state: lastOut[S]
-__global__ __launch_bounds__(BANK_W) void bank_deemp_kernel(const float* __restrict__ in, float* __restrict__ out, int frames, int S,
+// per channel (C = 1: float, DT = float; C = 2: stereo_t, DT = float2 = (l, r)), as deemp_kernel<C>;
+// state: lastOut[S] (C = 2: l[S], r[S])
+template <int C, typename DT>
+__global__ __launch_bounds__(BANK_W) void bank_deemp_kernel(const DT* __restrict__ in, DT* __restrict__ out, int frames, int S,
                                                             float alpha, float* __restrict__ st) {
-    __shared__ float X[BANK_F * BANK_W];
+    static_assert(sizeof(DT) == 4 * C, "one float per channel");
+    __shared__ DT X[BANK_F * BANK_W];
     const int k = blockIdx.x * BANK_W + threadIdx.x;
     if (k >= S) return;
-    float last = st[k];
     const float beta = 1 - alpha;                               // (1 - alpha): int - float -> float
-    bank_walk(X, in, out, frames, S, k, [&](float x, int, int, int) { return deemp_step(alpha, beta, x, last); });
-    st[k] = last;
+    if constexpr (C == 1) {
+        float last = st[k];
+        bank_walk(X, in, out, frames, S, k, [&](float x, int, int, int) { return deemp_step(alpha, beta, x, last); });
+        st[k] = last;
+    } else {
+        float l = st[k], r = st[S + k];
+        bank_walk(X, in, out, frames, S, k, [&](float2 x, int, int, int) {
+            const float yl = deemp_step(alpha, beta, x.x, l);
+            return make_float2(yl, deemp_step(alpha, beta, x.y, r));
+        });
+        st[k] = l;
+        st[S + k] = r;
+    }
 }
 
 // -------------------------------------------------------------------- Squelch

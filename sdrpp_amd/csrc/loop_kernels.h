@@ -25,7 +25,8 @@
 // same value. State (average amplitude, gain; DC offset) stays on the device between calls.
 #pragma once
 #include "serial_chunks.h"   // LOOP_CHUNK / LOOP_NT, amp_of / scale_of, serial_chunks
-#include "loop_steps.h"      // AgcParams, agc_step / agc_fixed_step, dcb_step, deemp_step (shared with the banks)
+#include "loop_steps.h"      // AgcParams, agc_step / agc_fixed_step, dcb_step, deemp_step, PllParams, pll_step,
+                             // stereo_matrix_value (shared with the banks)
 
 namespace sdrgpu {
 
@@ -141,27 +142,14 @@ __global__ void phase_kernel(const float2* __restrict__ in, float* __restrict__ 
     if (i < n) out[i] = atan2f(in[i].y, in[i].x);
 }
 
-// BroadcastFM stereo (demod/broadcast_fm.h:144-191):
-// Delays, conjugate, the two complex multiplies, x2, L = (L+R) + (L-R), R = (L+R) - (L-R),
-// written (l, r) as a float2 pair for the audio FIR. lmrDelay's input is RealToComplex of
-// the MPX, so its delayed imaginary part is exactly 0: the products are formed as the
-// reference forms them (0 * x terms included) and round identically.
+// BroadcastFM stereo (demod/broadcast_fm.h:144-191): the delays, then stereo_matrix_value (loop_steps.h),
+// written (l, r) as a float2 pair for the audio FIR.
 __global__ void stereo_matrix_kernel(const float* __restrict__ mpx, const float* __restrict__ hist, int delay,
                                      const float* __restrict__ vcoPhase, float2* __restrict__ lr, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float d = i < delay ? hist[i] : mpx[i - delay];       // Delay<float> / Delay<complex_t>.re
-    const float vr = cosf(vcoPhase[i]), vi = -sinf(vcoPhase[i]);   // Conjugate(phasor)
-    float ar = d, ai = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 2; k++) {                              // Multiply<complex_t>, twice
-        const float nr = (ar * vr) - (ai * vi);
-        const float ni = (ai * vr) + (ar * vi);
-        ar = nr;
-        ai = ni;
-    }
-    const float lmr = ar * 2.0f;
-    lr[i] = make_float2(d + lmr, d - lmr);
+    lr[i] = stereo_matrix_value(d, vcoPhase[i]);
 }
 
 
@@ -228,30 +216,14 @@ __global__ __launch_bounds__(LOOP_NT) void deemp_kernel(const float* __restrict_
     if (threadIdx.x == 0) *st = make_float2(last[0], last[1]);
 }
 
-// BroadcastFM's pilot PLL: loop/pll.h:64-70 + loop/phase_control_loop.h:59-66
-struct PllParams {
-    float alpha, beta, minPhase, maxPhase, phaseDelta, minFreq, maxFreq;
-};
-// The PLL recurrence (one workgroup): in place, th[i] = input phase -> the phase the VCO
-// outputs for sample i (math::phasor(pcl.phase) BEFORE advance). State (phase, freq) on device.
+// BroadcastFM's pilot PLL (pll_step, loop_steps.h), one workgroup: in place, th[i] = input phase -> the
+// phase the VCO outputs for sample i (math::phasor(pcl.phase) BEFORE advance). State (phase, freq) on device.
 __global__ __launch_bounds__(LOOP_NT) void pll_kernel(float* __restrict__ th, int count, PllParams p, float2* __restrict__ st) {
     __shared__ float T[LOOP_CHUNK];
     float phase = st->x, freq = st->y;
-    const float PI = 3.1415926535f;                            // FL_M_PI (math/constants.h:4)
     serial_chunks(
         count, [&](int i0, int i) { T[i] = th[i0 + i]; },
-        [&](int i) {
-            float diff = T[i] - phase;
-            T[i] = phase;
-            if (diff > PI) diff -= 2.0f * PI;                   // math::normalizePhase
-            else if (diff <= -PI) diff += 2.0f * PI;
-            freq += p.beta * diff;                              // PhaseControlLoop::advance
-            if (freq > p.maxFreq) freq = p.maxFreq;
-            else if (freq < p.minFreq) freq = p.minFreq;
-            phase += freq + (p.alpha * diff);
-            while (phase > p.maxPhase) phase -= p.phaseDelta;
-            while (phase < p.minPhase) phase += p.phaseDelta;
-        },
+        [&](int i) { T[i] = pll_step(p, T[i], phase, freq); },
         [&](int i0, int i) { th[i0 + i] = T[i]; });
     if (threadIdx.x == 0) *st = make_float2(phase, freq);
 }

@@ -1,9 +1,10 @@
 // Bit-exact recurrences: include this header only from a translation unit built with
 // -ffp-contract=off (loop_kernels.h says why).
 //
-// The per-sample steps of loop::AGC<T>, correction::DCBlocker<T> and filter::Deemphasis<T>, stated once
-// for the single-stream kernels (loop_kernels.h: one workgroup per stream) and the stream banks
-// (bank_audio_kernels.h: one lane per stream). Every step is written in the reference's operation order.
+// The per-sample steps of loop::AGC<T>, correction::DCBlocker<T>, filter::Deemphasis<T> and BroadcastFM's
+// pilot PLL, and its stereo matrix, stated once for the single-stream kernels (loop_kernels.h: one workgroup
+// per stream) and the stream banks (bank_audio_kernels.h, bank_wfm_kernels.h: one lane per stream). Every
+// step is written in the reference's operation order.
 #pragma once
 #include "serial_chunks.h"   // amp_of / scale_of
 
@@ -58,6 +59,45 @@ __device__ __forceinline__ float deemp_step(float alpha, float beta, float x, fl
     const float y = (alpha * x) + (beta * last);
     last = y;
     return y;
+}
+
+// BroadcastFM's pilot PLL: loop/pll.h:64-70 + loop/phase_control_loop.h:59-66
+struct PllParams {
+    float alpha, beta, minPhase, maxPhase, phaseDelta, minFreq, maxFreq;
+};
+// One sample: th = the input's phase; returns the phase the VCO outputs for it (math::phasor(pcl.phase)
+// BEFORE advance, pll.h:66-67), then advances (phase, freq).
+__device__ __forceinline__ float pll_step(const PllParams& p, float th, float& phase, float& freq) {
+    const float PI = 3.1415926535f;                             // FL_M_PI (math/constants.h:4)
+    const float vco = phase;
+    // (the two if / else-if chains of the reference as selects of the same values: a lane-per-stream wave
+    // would otherwise branch on its lanes' union at every sample)
+    const float d0 = th - phase;
+    const float diff = d0 > PI ? d0 - 2.0f * PI : (d0 <= -PI ? d0 + 2.0f * PI : d0);   // math::normalizePhase
+    const float f0 = freq + p.beta * diff;                      // PhaseControlLoop::advance
+    freq = f0 > p.maxFreq ? p.maxFreq : (f0 < p.minFreq ? p.minFreq : f0);
+    phase += freq + (p.alpha * diff);
+    while (phase > p.maxPhase) phase -= p.phaseDelta;
+    while (phase < p.minPhase) phase += p.phaseDelta;
+    return vco;
+}
+
+// BroadcastFM stereo (demod/broadcast_fm.h:173-190) of one sample: d = the delayed MPX (Delay<float>, and the
+// real part of Delay<complex_t>, whose input is RealToComplex of the MPX: its imaginary part is exactly 0),
+// vcoPhase = the PLL's output phase. Conjugate(phasor), the two complex multiplies as the reference forms
+// them (0 * x terms included, so they round identically), x2, then (l, r) = (L+R) + (L-R), (L+R) - (L-R).
+__device__ __forceinline__ float2 stereo_matrix_value(float d, float vcoPhase) {
+    const float vr = cosf(vcoPhase), vi = -sinf(vcoPhase);      // Conjugate(phasor)
+    float ar = d, ai = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {                               // Multiply<complex_t>, twice
+        const float nr = (ar * vr) - (ai * vi);
+        const float ni = (ai * vr) + (ar * vi);
+        ar = nr;
+        ai = ni;
+    }
+    const float lmr = ar * 2.0f;
+    return make_float2(d + lmr, d - lmr);
 }
 
 }  // namespace sdrgpu

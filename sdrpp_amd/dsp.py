@@ -765,11 +765,12 @@ class BankDCBlocker(Bank):
 
 
 class BankDeemphasis(Bank):
-    """dsp::filter::Deemphasis<float> per stream."""
+    """dsp::filter::Deemphasis<float> per stream; ``stereo=True``: Deemphasis<stereo_t>, complex64 rows of (l, r)."""
 
-    def __init__(self, streams, tau, samplerate, device=0):
-        super().__init__(_make(lib.sdrgpu_bank_deemphasis_create, device, int(streams), float(tau), float(samplerate)), np.float32,
-                         np.float32)
+    def __init__(self, streams, tau, samplerate, device=0, stereo=False):
+        fn = lib.sdrgpu_bank_deemphasis_stereo_create if stereo else lib.sdrgpu_bank_deemphasis_create
+        npd = np.complex64 if stereo else np.float32
+        super().__init__(_make(fn, device, int(streams), float(tau), float(samplerate)), npd, npd)
 
 
 class BankSquelch(Bank):
@@ -891,6 +892,36 @@ class BankRationalResampler(_RateBank):
 
     def __init__(self, streams, in_sr, out_sr, complex_data=True, device=0):
         super().__init__(lib.sdrgpu_bank_rational_resampler_create, streams, complex_data, device, float(in_sr), float(out_sr))
+
+
+class BankFIRComplex(Bank):
+    """dsp::filter::FIR<complex_t, complex_t> per stream: complex taps shared by all streams, complex64 out.
+    ``real_input=True``: float32 rows, convert::RealToComplex first in the same launch."""
+
+    def __init__(self, streams, taps, real_input=False, device=0):
+        t = np.ascontiguousarray(taps, np.complex64)
+        self._taps = t
+        h = _make(lib.sdrgpu_bank_fir_complex_create, device, int(streams), F32 if real_input else C64, _fptr(t), int(t.shape[0]))
+        super().__init__(h, np.float32 if real_input else np.complex64, np.complex64)
+
+
+class BankStereoDecoder(Bank):
+    """The stereo decoder of dsp::demod::BroadcastFM per stream (pilot filter -> PLL -> matrix): float32 MPX ->
+    complex64 (l, r) = (re, im)."""
+
+    def __init__(self, streams, samplerate, device=0):
+        super().__init__(_make(lib.sdrgpu_bank_stereo_decoder_create, device, int(streams), float(samplerate)), np.float32,
+                         np.complex64)
+
+
+class BankBroadcastFM(Bank):
+    """dsp::demod::BroadcastFM per stream, without the RDS branch: complex64 -> complex64 (l, r) = (re, im);
+    arguments as BroadcastFM."""
+
+    def __init__(self, streams, deviation, samplerate, low_pass=True, stereo=True, device=0):
+        h = _make(lib.sdrgpu_bank_broadcast_fm_create, device, int(streams), float(deviation), float(samplerate), int(bool(stereo)),
+                  int(bool(low_pass)))
+        super().__init__(h, np.complex64, np.complex64)
 
 
 class DCBlocker(Block):
