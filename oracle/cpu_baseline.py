@@ -30,20 +30,31 @@ BLK = 1000000        # SpeedTester block (speed_tester.h:37: 1e6 samples)
 
 def native_oracle():
     """Build the oracle with -march=native for the host this runs on (outside the repo tree)."""
-    out_dir = os.path.join(os.environ.get("TMPDIR", "/tmp"), "sdrgpu_cpu_baseline")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libsdr_oracle_native.so")
+    import hashlib
     src = os.path.join(HERE, "sdr_oracle.c")
     fast = os.path.join(HERE, "cpu_fast.c")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(fast)):
-        # -ffp-contract=fast: the dot products use FMA like VOLK's *_avx2_fma kernels (this copy
-        # is only timed; the in-tree checker build keeps -ffp-contract=off)
-        cmd = ["gcc", "-O3", "-march=native", "-ffp-contract=fast", "-fno-fast-math", "-fPIC", "-shared",
-               "-o", so, src, fast, "-lm"]
-        try:
+    # The copy is named after its sources' contents: the directory outlives a checkout and is shared by
+    # every checkout on the host, and a copy built from another version of the sources lacks the functions
+    # oracle.py binds (file times do not tell: a checkout's files can be older than another's build).
+    h = hashlib.sha256()
+    for path in (src, fast, os.path.join(HERE, "sdr_oracle.h"),
+                 os.path.join(HERE, "..", "sdrpp_amd", "csrc", "decim_plans_data.h")):
+        with open(path, "rb") as f:
+            h.update(f.read())
+    try:
+        out_dir = os.path.join(os.environ.get("TMPDIR", "/tmp"), "sdrgpu_cpu_baseline")
+        os.makedirs(out_dir, exist_ok=True)
+        so = os.path.join(out_dir, f"libsdr_oracle_native_{h.hexdigest()[:16]}.so")
+        if not os.path.exists(so):
+            # -ffp-contract=fast: the dot products use FMA like VOLK's *_avx2_fma kernels (this copy
+            # is only timed; the in-tree checker build keeps -ffp-contract=off)
+            tmp = f"{so}.{os.getpid()}.tmp"
+            cmd = ["gcc", "-O3", "-march=native", "-ffp-contract=fast", "-fno-fast-math", "-fPIC", "-shared",
+                   "-o", tmp, src, fast, "-lm"]
             subprocess.check_call(cmd, cwd=HERE, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        except (OSError, subprocess.CalledProcessError):
-            return None
+            os.replace(tmp, so)   # (whole or not at all: the streams' workers may be building it too)
+    except (OSError, subprocess.CalledProcessError):
+        return None
     return so
 
 

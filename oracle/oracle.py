@@ -43,6 +43,7 @@ def _load():
         "orc_fft_logmag": (None, [vp, i, i, vp, vp, vp]),
         "orc_fir_create": (vp, [i, i, vp, i, i, i]),
         "orc_fir_set_taps": (None, [vp, vp, i]),
+        "orc_fir_set_decimation": (None, [vp, i]),
         "orc_fir_reset": (None, [vp]),
         "orc_fir_process": (i, [vp, vp, i, vp]),
         "orc_fir_destroy": (None, [vp]),
@@ -54,6 +55,7 @@ def _load():
         "orc_xlator_destroy": (None, [vp]),
         "orc_quad_create": (vp, [d]),
         "orc_quad_reset": (None, [vp]),
+        "orc_quad_set_deviation": (None, [vp, d]),
         "orc_quad_process": (i, [vp, vp, i, vp]),
         "orc_quad_destroy": (None, [vp]),
         "orc_pdec_create": (vp, [i, i, i]),
@@ -66,16 +68,20 @@ def _load():
         "orc_poly_destroy": (None, [vp]),
         "orc_rres_create": (vp, [i, d, d, i]),
         "orc_rres_process": (i, [vp, vp, i, vp]),
+        "orc_rres_reset": (None, [vp]),
         "orc_rres_info": (i, [vp, vp, vp, vp, vp, vp]),
         "orc_rres_destroy": (None, [vp]),
         "orc_vfo_create": (vp, [d, d, d, d, i]),
         "orc_vfo_process": (i, [vp, vp, i, vp]),
+        "orc_vfo_set_offset": (None, [vp, d]),
+        "orc_vfo_reset": (None, [vp]),
         "orc_vfo_destroy": (None, [vp]),
         "orc_wfm_create": (vp, [d, d, i, i]),
         "orc_wfm_process": (i, [vp, vp, i, vp]),
         "orc_wfm_destroy": (None, [vp]),
         "orc_fm_create": (vp, [d, d, i, i, i]),
         "orc_fm_process": (i, [vp, vp, i, vp]),
+        "orc_fm_reset": (None, [vp]),
         "orc_fm_destroy": (None, [vp]),
         "orc_agc_create": (vp, [i, d, d, d, d, d, d]),
         "orc_agc_set_enabled": (None, [vp, i]),
@@ -107,6 +113,10 @@ def _load():
         "orc_vfo_signal_info": (None, [vp, i, d, d, d, vp, vp]),
         "orc_ddcfm_create": (vp, [d, vp, i, i, d, i]),
         "orc_ddcfm_process": (i, [vp, vp, i, vp]),
+        "orc_ddcfm_set_taps": (None, [vp, vp, i]),
+        "orc_ddcfm_set_decimation": (None, [vp, i]),
+        "orc_ddcfm_set_deviation": (None, [vp, d]),
+        "orc_ddcfm_reset": (None, [vp]),
         "orc_ddcfm_destroy": (None, [vp]),
         "orc_wav_encode": (i, [i, vp, i, vp]),
         "orc_chain_create": (vp, [d, i, d, i]),
@@ -281,6 +291,9 @@ class FIR(_Obj):
         t = t.astype(np.complex64 if np.iscomplexobj(t) else np.float32)
         lib.orc_fir_set_taps(self._h, _p(t), t.shape[0])
 
+    def set_decimation(self, decim):
+        lib.orc_fir_set_decimation(self._h, int(decim))
+
 
 class Xlator(_Obj):
     _destroy = lib.orc_xlator_destroy
@@ -294,6 +307,9 @@ class Xlator(_Obj):
     def set_offset(self, offset_rad):
         lib.orc_xlator_set_offset(self._h, float(offset_rad))
 
+    def reset(self):
+        lib.orc_xlator_reset(self._h)
+
 
 class Quadrature(_Obj):
     _destroy = lib.orc_quad_destroy
@@ -303,6 +319,12 @@ class Quadrature(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_quad_process)
+
+    def set_deviation(self, deviation_rad):
+        lib.orc_quad_set_deviation(self._h, float(deviation_rad))
+
+    def reset(self):
+        lib.orc_quad_reset(self._h)
 
 
 class PowerDecimator(_Obj):
@@ -314,6 +336,9 @@ class PowerDecimator(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_pdec_process)
+
+    def reset(self):
+        lib.orc_pdec_reset(self._h)
 
 
 class PolyphaseResampler(_Obj):
@@ -328,6 +353,9 @@ class PolyphaseResampler(_Obj):
     def process(self, x):
         return super().process(x, lib.orc_poly_process)
 
+    def reset(self):
+        lib.orc_poly_reset(self._h)
+
 
 class RationalResampler(_Obj):
     _destroy = lib.orc_rres_destroy
@@ -339,6 +367,9 @@ class RationalResampler(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_rres_process)
+
+    def reset(self):
+        lib.orc_rres_reset(self._h)
 
     def info(self):
         v = [ctypes.c_int() for _ in range(5)]
@@ -355,6 +386,12 @@ class RxVFO(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_vfo_process)
+
+    def set_offset(self, offset):
+        lib.orc_vfo_set_offset(self._h, float(offset))
+
+    def reset(self):
+        lib.orc_vfo_reset(self._h)
 
 
 STEREO = np.dtype([("l", np.float32), ("r", np.float32)])
@@ -395,6 +432,19 @@ class DDCFM(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_ddcfm_process)
+
+    def set_taps(self, taps):
+        self._t = np.ascontiguousarray(taps, np.float32)
+        lib.orc_ddcfm_set_taps(self._h, _p(self._t), len(self._t))
+
+    def set_decimation(self, decim):
+        lib.orc_ddcfm_set_decimation(self._h, int(decim))
+
+    def set_deviation(self, deviation_rad):
+        lib.orc_ddcfm_set_deviation(self._h, float(deviation_rad))
+
+    def reset(self):
+        lib.orc_ddcfm_reset(self._h)
 
 
 class Deemphasis(_Obj):
@@ -477,6 +527,9 @@ class FM(_Obj):
 
     def process(self, x):
         return super().process(x, lib.orc_fm_process)
+
+    def reset(self):
+        lib.orc_fm_reset(self._h)
 
 
 class AGC(_Obj):

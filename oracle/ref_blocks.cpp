@@ -8,10 +8,15 @@
 //   ref_blocks <mode> <calls> [parameters...]
 //
 // <calls> is a comma list run in order: a number is one process() call of that many input samples
-// (0 included); for the MM modes `r` calls reset(), `o<omega>` setOmega() and `i<P>x<T>`
-// setInterpParams(). Input samples are raw on stdin (as many as the calls sum to). stdout: int32
-// number of process() calls, int32 output count of each, then every call's outputs, raw, in order.
-// The rds mode appends every call's bits (uint8) after the soft symbols.
+// (0 included); `r` calls reset() (MM and the channel-chain modes), `o<omega>` setOmega() and `i<P>x<T>`
+// setInterpParams() (MM); for the channel-chain modes `w<rad>` is the xlator's setOffset(), `f<hz>`
+// RxVFO::setOffset(), `d<n>` setDecimation(), `t<k>` setTaps() to the k-th tap set and `v<rad>`
+// setDeviation(). Input samples are raw on stdin (as many as the calls sum to); the modes that take
+// tap sets (fir_*, poly_*, ddc, ddcfm) read them first: int32 number of sets, then per set int32 count
+// and the taps, raw. They stay allocated for the whole run (tap<T> is not owned by the block). stdout:
+// int32 number of process() calls, int32 output count of each, then every call's outputs, raw, in
+// order. The rds mode appends every call's bits (uint8) after the soft symbols, the ddcfm mode every
+// call's FIR-stage outputs (complex_t).
 //
 //   fastagc_f|fastagc_c  setPoint maxGain rate initGain     loop::FastAGC<float|complex_t>
 //   costas  order bandwidth [initPhase initFreq minFreq maxFreq]
@@ -28,6 +33,17 @@
 //   psk  order symbolrate samplerate rrcTaps rrcBeta agcRate costasBw omegaGain muGain omegaRelLimit
 //   gfsk  symbolrate samplerate deviation rrcTaps rrcBeta omegaGain muGain omegaRelLimit
 //   rds                                                     the blocks and calls of the radio module's wfm.h:57-68
+// Channel chain:
+//   xlator  w                                               channel::FrequencyXlator
+//   fir_ff|fir_cf|fir_cc  D                                 filter::DecimatingFIR<D, T> for D > 1, filter::FIR<D, T> for D = 1
+//   pdec_f|pdec_c  ratio                                    multirate::PowerDecimator<float|complex_t>
+//   poly_f|poly_c  interp decim                             multirate::PolyphaseResampler<float|complex_t>
+//   rres_f|rres_c  in out                                   multirate::RationalResampler<float|complex_t>
+//   rxvfo  in out bw offset                                 channel::RxVFO
+//   quad  dev                                               demod::Quadrature
+//   fm  samplerate bandwidth lowPass highPass               demod::FM<float>
+//   ddc  w D                                                FrequencyXlator -> DecimatingFIR<complex_t, float>, block by block
+//   ddcfm  w D dev                                          the same -> Quadrature
 // Design code (no stdin, <calls> ignored; stdout float32 only):
 //   rrc  count beta Ts                                      taps::rootRaisedCosine<float>
 //   mmbank  P T                                             the bank MM builds for itself, [P][T]
@@ -58,12 +74,19 @@
 #include <dsp/math/hz_to_rads.h>
 #include <dsp/demod/psk.h>
 #include <dsp/demod/gfsk.h>
+#include <dsp/channel/rx_vfo.h>
+#include <dsp/filter/decimating_fir.h>
+#include <dsp/multirate/power_decimator.h>
+#include <dsp/multirate/polyphase_resampler.h>
+#include <dsp/multirate/rational_resampler.h>
+#include <dsp/demod/quadrature.h>
+#include <dsp/demod/fm.h>
 
 using dsp::complex_t;
 using dsp::stereo_t;
 
 struct Op {
-    char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams
+    char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams, 'w' 'f' 'd' 't' 'v' the chain's setters
     int count = 0, a = 0, b = 0;
     double v = 0.0;
 };
@@ -82,6 +105,8 @@ static std::vector<Op> parseCalls(const char* s) {
         if (tok[0] == 'r') { op.kind = 'r'; }
         else if (tok[0] == 'o') { op.kind = 'o'; op.v = strtod(tok.c_str() + 1, NULL); }
         else if (tok[0] == 'i') { op.kind = 'i'; sscanf(tok.c_str() + 1, "%dx%d", &op.a, &op.b); }
+        else if (tok[0] == 'w' || tok[0] == 'f' || tok[0] == 'v') { op.kind = tok[0]; op.v = strtod(tok.c_str() + 1, NULL); }
+        else if (tok[0] == 'd' || tok[0] == 't') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
         else { op.kind = 'p'; op.count = atoi(tok.c_str()); }
         ops.push_back(op);
     }
@@ -95,6 +120,9 @@ static std::vector<T> readInput(size_t n) {
     return x;
 }
 
+static size_t outPerIn = 1;          // output capacity per input sample (the interpolating resamplers: more than 1)
+static std::vector<uint8_t> tail;    // written after everything else (ddcfm: the FIR-stage outputs)
+
 // Runs the process() calls of `ops` over stdin; `other` handles the remaining kinds.
 template <class I, class O>
 static int runCalls(const std::vector<Op>& ops, std::function<int(int, I*, O*)> proc,
@@ -103,7 +131,7 @@ static int runCalls(const std::vector<Op>& ops, std::function<int(int, I*, O*)> 
     size_t total = 0;
     for (auto& op : ops) { total += op.kind == 'p' ? op.count : 0; }
     std::vector<I> x = readInput<I>(total);
-    std::vector<O> y(total + 1);
+    std::vector<O> y((total + ops.size()) * outPerIn + 1);
     std::vector<int32_t> counts;
     size_t ip = 0, op_ = 0;
     for (auto& op : ops) {
@@ -127,6 +155,7 @@ static int runCalls(const std::vector<Op>& ops, std::function<int(int, I*, O*)> 
     fwrite(counts.data(), sizeof(int32_t), counts.size(), stdout);
     fwrite(y.data(), sizeof(O), op_, stdout);
     if (second) { fwrite(second->data(), 1, second->size(), stdout); }
+    fwrite(tail.data(), 1, tail.size(), stdout);
     return 0;
 }
 
@@ -240,6 +269,127 @@ static int runRDS(const std::vector<Op>& ops) {
     });
 }
 
+// ------------------------------------------------------------------ channel chain
+template <class T>
+static std::vector<dsp::tap<T>> readTapSets() {
+    int32_t ns = 0, n = 0;
+    if (fread(&ns, sizeof(ns), 1, stdin) != 1 || ns < 1) { fprintf(stderr, "ref_blocks: no tap sets\n"); exit(3); }
+    std::vector<dsp::tap<T>> sets(ns);
+    for (auto& t : sets) {
+        if (fread(&n, sizeof(n), 1, stdin) != 1 || n < 1) { fprintf(stderr, "ref_blocks: bad tap set\n"); exit(3); }
+        t = dsp::taps::alloc<T>(n);
+        if (fread(t.taps, sizeof(T), n, stdin) != (size_t)n) { fprintf(stderr, "ref_blocks: short tap set\n"); exit(3); }
+    }
+    return sets;
+}
+
+static void badOp(const Op& op) {
+    fprintf(stderr, "ref_blocks: this mode has no op '%c'\n", op.kind);
+    exit(2);
+}
+
+template <class T>
+static dsp::tap<T>& tapSet(std::vector<dsp::tap<T>>& sets, const Op& op) {
+    if (op.a < 0 || op.a >= (int)sets.size()) { fprintf(stderr, "ref_blocks: no tap set %d\n", op.a); exit(2); }
+    return sets[op.a];
+}
+
+template <class D, class T>
+static int runFIR(const std::vector<Op>& ops, int decim) {
+    static std::vector<dsp::tap<T>> sets = readTapSets<T>();
+    if (decim > 1) {
+        auto& b = zeroed<dsp::filter::DecimatingFIR<D, T>>();
+        b.init(NULL, sets[0], decim);
+        return runCalls<D, D>(ops, [&](int n, D* in, D* out) { return b.process(n, in, out); }, [&](const Op& op) {
+            if (op.kind == 'r') { b.reset(); }
+            else if (op.kind == 't') { b.setTaps(tapSet(sets, op)); }
+            else if (op.kind == 'd') { b.setDecimation(op.a); }
+            else { badOp(op); }
+        });
+    }
+    auto& b = zeroed<dsp::filter::FIR<D, T>>();
+    b.init(NULL, sets[0]);
+    return runCalls<D, D>(ops, [&](int n, D* in, D* out) { return b.process(n, in, out); }, [&](const Op& op) {
+        if (op.kind == 'r') { b.reset(); }
+        else if (op.kind == 't') { b.setTaps(tapSet(sets, op)); }
+        else { badOp(op); }
+    });
+}
+
+template <class T>
+static int runPdec(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<dsp::multirate::PowerDecimator<T>>();
+    b.init(NULL, atoi(p[0]));
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); },
+                          [&](const Op& op) { if (op.kind == 'r') { b.reset(); } else { badOp(op); } });
+}
+
+template <class T>
+static int runPoly(const std::vector<Op>& ops, char** p) {
+    static std::vector<dsp::tap<float>> sets = readTapSets<float>();
+    auto& b = zeroed<dsp::multirate::PolyphaseResampler<T>>();
+    b.init(NULL, atoi(p[0]), atoi(p[1]), sets[0]);
+    outPerIn = atoi(p[0]) / atoi(p[1]) + 1;
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); },
+                          [&](const Op& op) { if (op.kind == 'r') { b.reset(); } else { badOp(op); } });
+}
+
+template <class T>
+static int runRres(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<dsp::multirate::RationalResampler<T>>();
+    b.init(NULL, atof(p[0]), atof(p[1]));
+    outPerIn = (size_t)(atof(p[1]) / atof(p[0])) + 1;
+    return runCalls<T, T>(ops, [&](int n, T* in, T* out) { return b.process(n, in, out); },
+                          [&](const Op& op) { if (op.kind == 'r') { b.reset(); } else { badOp(op); } });
+}
+
+static int runRxVFO(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<dsp::channel::RxVFO>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]));
+    outPerIn = (size_t)(atof(p[1]) / atof(p[0])) + 1;
+    return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); },
+                                          [&](const Op& op) {
+        if (op.kind == 'r') { b.reset(); }
+        else if (op.kind == 'f') { b.setOffset(op.v); }
+        else { badOp(op); }
+    });
+}
+
+// xlator -> DecimatingFIR<complex_t, float> [-> Quadrature], each block's process() called in the order
+// the streams would connect them; reset() resets every block of the chain
+static int runDDC(const std::vector<Op>& ops, char** p, bool fm) {
+    static std::vector<dsp::tap<float>> sets = readTapSets<float>();
+    auto& x = zeroed<dsp::channel::FrequencyXlator>();
+    auto& f = zeroed<dsp::filter::DecimatingFIR<complex_t, float>>();
+    auto& q = zeroed<dsp::demod::Quadrature>();
+    x.init(NULL, atof(p[0]));
+    f.init(NULL, sets[0], atoi(p[1]));
+    if (fm) { q.init(NULL, atof(p[2])); }
+    size_t cap = 1;
+    for (auto& op : ops) { cap = std::max<size_t>(cap, op.count + 1); }
+    std::vector<complex_t> a(cap), z(cap);
+    auto other = [&](const Op& op) {
+        if (op.kind == 'r') { x.reset(); f.reset(); if (fm) { q.reset(); } }
+        else if (op.kind == 't') { f.setTaps(tapSet(sets, op)); }
+        else if (op.kind == 'd') { f.setDecimation(op.a); }
+        else if (op.kind == 'v' && fm) { q.setDeviation(op.v); }
+        else { badOp(op); }
+    };
+    if (!fm) {
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) {
+            x.process(n, in, a.data());
+            return f.process(n, a.data(), out);
+        }, other);
+    }
+    return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) {
+        x.process(n, in, a.data());
+        int m = f.process(n, a.data(), z.data());
+        const uint8_t* raw = (const uint8_t*)z.data();
+        tail.insert(tail.end(), raw, raw + m * sizeof(complex_t));
+        return q.process(m, z.data(), out);
+    }, other);
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { return 2; }
     std::string mode = argv[1];
@@ -299,6 +449,45 @@ int main(int argc, char** argv) {
         return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) { return b.process(n, in, out); });
     }
     if (mode == "rds" && np == 0) { return runRDS(ops); }
+
+    if (mode == "xlator" && np == 1) {
+        auto& b = zeroed<dsp::channel::FrequencyXlator>();
+        b.init(NULL, atof(p[0]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); },
+                                              [&](const Op& op) {
+            if (op.kind == 'r') { b.reset(); }
+            else if (op.kind == 'w') { b.setOffset(op.v); }
+            else { badOp(op); }
+        });
+    }
+    if (mode == "fir_ff" && np == 1) { return runFIR<float, float>(ops, atoi(p[0])); }
+    if (mode == "fir_cf" && np == 1) { return runFIR<complex_t, float>(ops, atoi(p[0])); }
+    if (mode == "fir_cc" && np == 1) { return runFIR<complex_t, complex_t>(ops, atoi(p[0])); }
+    if (mode == "pdec_f" && np == 1) { return runPdec<float>(ops, p); }
+    if (mode == "pdec_c" && np == 1) { return runPdec<complex_t>(ops, p); }
+    if (mode == "poly_f" && np == 2) { return runPoly<float>(ops, p); }
+    if (mode == "poly_c" && np == 2) { return runPoly<complex_t>(ops, p); }
+    if (mode == "rres_f" && np == 2) { return runRres<float>(ops, p); }
+    if (mode == "rres_c" && np == 2) { return runRres<complex_t>(ops, p); }
+    if (mode == "rxvfo" && np == 4) { return runRxVFO(ops, p); }
+    if (mode == "quad" && np == 1) {
+        auto& b = zeroed<dsp::demod::Quadrature>();
+        b.init(NULL, atof(p[0]));
+        return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) { return b.process(n, in, out); },
+                                          [&](const Op& op) {
+            if (op.kind == 'r') { b.reset(); }
+            else if (op.kind == 'v') { b.setDeviation(op.v); }
+            else { badOp(op); }
+        });
+    }
+    if (mode == "fm" && np == 4) {
+        auto& b = zeroed<dsp::demod::FM<float>>();
+        b.init(NULL, atof(p[0]), atof(p[1]), atoi(p[2]) != 0, atoi(p[3]) != 0);
+        return runCalls<complex_t, float>(ops, [&](int n, complex_t* in, float* out) { return b.process(n, in, out); },
+                                          [&](const Op& op) { if (op.kind == 'r') { b.reset(); } else { badOp(op); } });
+    }
+    if (mode == "ddc" && np == 2) { return runDDC(ops, p, false); }
+    if (mode == "ddcfm" && np == 3) { return runDDC(ops, p, true); }
 
     if (mode == "rrc" && np == 3) {
         dsp::tap<float> t = dsp::taps::rootRaisedCosine<float>(atoi(p[0]), atof(p[1]), atof(p[2]));

@@ -10,7 +10,7 @@
 // * fftwf_*: a direct O(n^2) DFT evaluated in fp64, unnormalised in both directions as FFTW is, each
 //   output rounded once to fp32. noise_reduction/fm_if.h with at most 32 bins is its only user;
 // * the five host symbols block.h's thread wrapper refers to, as no-ops (the probe never starts a
-//   thread).
+//   thread), and flog::logImpl, which drops the message (RationalResampler logs its plan).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +20,7 @@
 #include <volk/volk.h>
 #include <fftw3.h>
 #include <utils/threading.h>
+#include <utils/flog.h>
 
 // ---------------------------------------------------------------- VOLK
 size_t volk_get_alignment(void) { return 64; }
@@ -111,6 +112,61 @@ void volk_32fc_deinterleave_real_32f(float* iBuffer, const lv_32fc_t* complexVec
     for (unsigned int i = 0; i < num_points; i++) { iBuffer[i] = in[2 * i]; }
 }
 
+// VOLK's generic rotator as published (volk_32fc_s32fc_x2_rotator_32fc_generic): out = in * phase, phase
+// *= phase_inc in fp32, phase renormalised after every 512 samples and once more at the end of a call
+// that leaves a remainder. With -DREF_ROT64 the phase is carried in fp64 beside the block's fp32 copy
+// (found again by its address; a copy the block has rewritten, as reset() does, is taken over) and each
+// output is the fp64 product rounded once: that build exists only to measure how far the reference's
+// own fp32 phase recurrence drifts from the phase it stands for.
+static const unsigned ROTATOR_RELOAD = 512;
+
+#ifdef REF_ROT64
+#include <map>
+void volk_32fc_s32fc_x2_rotator_32fc(lv_32fc_t* outVector, const lv_32fc_t* inVector, const lv_32fc_t phase_inc, lv_32fc_t* phase,
+                                     unsigned int num_points) {
+    static std::map<const lv_32fc_t*, std::complex<double>> carried;
+    auto it = carried.find(phase);
+    if (it == carried.end() || lv_32fc_t((float)it->second.real(), (float)it->second.imag()) != *phase) {
+        it = carried.insert_or_assign(phase, std::complex<double>(phase->real(), phase->imag())).first;
+    }
+    double pr = it->second.real(), pi = it->second.imag();
+    const double dr = phase_inc.real(), di = phase_inc.imag();
+    for (unsigned int i = 0; i < num_points; i++) {
+        const double ar = inVector[i].real(), ai = inVector[i].imag();
+        outVector[i] = lv_cmake((float)(ar * pr - ai * pi), (float)(ar * pi + ai * pr));
+        const double nr = pr * dr - pi * di, ni = pr * di + pi * dr;
+        pr = nr;
+        pi = ni;
+        if ((i + 1) % ROTATOR_RELOAD == 0 || i + 1 == num_points) {
+            const double h = hypot(pr, pi);
+            pr /= h;
+            pi /= h;
+        }
+    }
+    it->second = std::complex<double>(pr, pi);
+    *phase = lv_cmake((float)pr, (float)pi);
+}
+#else
+void volk_32fc_s32fc_x2_rotator_32fc(lv_32fc_t* outVector, const lv_32fc_t* inVector, const lv_32fc_t phase_inc, lv_32fc_t* phase,
+                                     unsigned int num_points) {
+    float pr = phase->real(), pi = phase->imag();
+    const float dr = phase_inc.real(), di = phase_inc.imag();
+    for (unsigned int i = 0; i < num_points; i++) {
+        const float ar = inVector[i].real(), ai = inVector[i].imag();
+        outVector[i] = lv_cmake((ar * pr) - (ai * pi), (ar * pi) + (ai * pr));
+        const float nr = (pr * dr) - (pi * di), ni = (pr * di) + (pi * dr);
+        pr = nr;
+        pi = ni;
+        if ((i + 1) % ROTATOR_RELOAD == 0 || i + 1 == num_points) {
+            const float h = hypotf(pr, pi);
+            pr /= h;
+            pi /= h;
+        }
+    }
+    *phase = lv_cmake(pr, pi);
+}
+#endif
+
 // ---------------------------------------------------------------- FFTW (single precision)
 struct fftwf_plan_s {
     int n, sign;
@@ -162,6 +218,8 @@ void fftwf_destroy_plan(fftwf_plan p) { delete p; }
 namespace flog {
     void exception(const std::exception&) {}
     void exception() {}
+    void logImpl(flog::Type, std::string, const std::chrono::time_point<std::chrono::steady_clock>,
+                 const std::shared_ptr<const stack_trace>) {}
 }
 
 namespace threading {

@@ -396,6 +396,12 @@ void orc_fir_reset(orc_fir* f) {
     f->offset = 0;
 }
 
+/* DecimatingFIR::setDecimation (decimating_fir.h:28-35): the phase restarts, the history stays */
+void orc_fir_set_decimation(orc_fir* f, int decim) {
+    f->decim = decim < 1 ? 1 : decim;
+    f->offset = 0;
+}
+
 int orc_fir_process(orc_fir* f, const float* in, int count, float* out) {
     int e = esz(f->dtype), h = f->ntaps - 1;
     if (f->cap < count) {
@@ -463,8 +469,9 @@ void orc_xlator_set_offset(orc_xlator* x, double offset_rad) {
     x->origin = fmodl(x->origin + (long double)x->w * (long double)x->n, twopi);
     x->n = 0;
     x->w = orc_xlator_effective_omega(offset_rad);
+    x->dr = (float)cos(offset_rad); x->di = (float)sin(offset_rad);
 }
-void orc_xlator_reset(orc_xlator* x) { x->n = 0; x->origin = 0; }   /* reset(): phase = 1+0j */
+void orc_xlator_reset(orc_xlator* x) { x->n = 0; x->origin = 0; x->pr = 1.0f; x->pi = 0.0f; }   /* reset(): phase = 1+0j */
 int orc_xlator_process(orc_xlator* x, const float* in, int count, float* out) {
     if (x->fast) {   /* CPU baseline: the rotator on 8 lanes per vector (cpu_fast.c) */
         cf_rotate(in, out, count, &x->pr, &x->pi, x->dr, x->di, &x->cnt);
@@ -493,6 +500,7 @@ orc_quad* orc_quad_create(double deviation_rad) {
     return q;
 }
 void orc_quad_reset(orc_quad* q) { q->dre = 0.0f; q->dim = 0.0f; }
+void orc_quad_set_deviation(orc_quad* q, double deviation_rad) { q->inv = (float)(1.0 / deviation_rad); }   /* quadrature.h:29-33 */
 int orc_quad_process(orc_quad* q, const float* in, int count, float* out) {
     if (q->fast) {   /* CPU baseline: 16 outputs per vector, polynomial atan (cpu_fast.c) */
         cf_quad(in, count, out, &q->dre, &q->dim, q->inv);
@@ -639,13 +647,16 @@ int orc_rres_process(orc_rres* r, const float* in, int count, float* out) {
     default: memmove(out, in, sizeof(float) * (size_t)count * esz(r->dtype)); return count;
     }
 }
+/* reset() (rational_resampler.h:42-49): both members, whichever the mode uses */
+void orc_rres_reset(orc_rres* r) { if (r->pd) orc_pdec_reset(r->pd); if (r->pp) orc_poly_reset(r->pp); }
 void orc_rres_destroy(orc_rres* r) { if (!r) return; orc_pdec_destroy(r->pd); orc_poly_destroy(r->pp); free(r); }
 
 /* ------------------------------------------------------------------ RxVFO */
 /* channel/rx_vfo.h:24-121 */
-struct orc_vfo { orc_xlator* x; orc_rres* rr; orc_fir* lpf; int filterNeeded; float* tmp; int cap; };
+struct orc_vfo { orc_xlator* x; orc_rres* rr; orc_fir* lpf; int filterNeeded; float* tmp; int cap; double inSr; };
 orc_vfo* orc_vfo_create(double inSr, double outSr, double bw, double offset, int precise) {
     orc_vfo* v = (orc_vfo*)calloc(1, sizeof(orc_vfo));
+    v->inSr = inSr;
     v->x = precise ? orc_xlator_create(hz_to_rads(-offset, inSr)) : orc_xlator_create_fast(hz_to_rads(-offset, inSr));
     v->rr = orc_rres_create(ORC_C64, inSr, outSr, precise);
     v->filterNeeded = (bw != outSr);
@@ -677,6 +688,9 @@ int orc_vfo_process(orc_vfo* v, const float* in, int count, float* out) {
     if (v->filterNeeded) orc_fir_process(v->lpf, out, count, out);
     return count;
 }
+/* setOffset (rx_vfo.h:72-77) and reset (:79-87: the filter too, needed or not) */
+void orc_vfo_set_offset(orc_vfo* v, double offset) { orc_xlator_set_offset(v->x, hz_to_rads(-offset, v->inSr)); }
+void orc_vfo_reset(orc_vfo* v) { orc_xlator_reset(v->x); orc_rres_reset(v->rr); orc_fir_reset(v->lpf); }
 void orc_vfo_destroy(orc_vfo* v) { if (!v) return; orc_xlator_destroy(v->x); orc_rres_destroy(v->rr); orc_fir_destroy(v->lpf); free(v->tmp); free(v); }
 
 /* ------------------------------------------------------- BroadcastFM mono */
@@ -849,6 +863,7 @@ int orc_fm_process(orc_fm* f, const float* in, int count, float* out) {
     if (f->filtering) orc_fir_process(f->fir, out, count, out);
     return count;
 }
+void orc_fm_reset(orc_fm* f) { orc_quad_reset(f->q); orc_fir_reset(f->fir); }   /* fm.h:77-84 */
 void orc_fm_destroy(orc_fm* f) { if (!f) return; orc_quad_destroy(f->q); orc_fir_destroy(f->fir); free(f); }
 
 /* --------------------------------------------------------------------- AGC */
@@ -1242,6 +1257,11 @@ int orc_ddcfm_process(orc_ddcfm* d, const float* in, int count, float* out) {
     }
     return total;
 }
+/* the three blocks' own setters and resets (decimating_fir.h:19-43, quadrature.h:29-33, :58-68) */
+void orc_ddcfm_set_taps(orc_ddcfm* d, const float* taps, int ntaps) { orc_fir_set_taps(d->f, taps, ntaps); }
+void orc_ddcfm_set_decimation(orc_ddcfm* d, int decim) { orc_fir_set_decimation(d->f, decim); }
+void orc_ddcfm_set_deviation(orc_ddcfm* d, double deviationRad) { orc_quad_set_deviation(d->q, deviationRad); }
+void orc_ddcfm_reset(orc_ddcfm* d) { orc_xlator_reset(d->x); orc_fir_reset(d->f); orc_quad_reset(d->q); }
 void orc_ddcfm_destroy(orc_ddcfm* d) {
     if (!d) return;
     orc_xlator_destroy(d->x); orc_fir_destroy(d->f); orc_quad_destroy(d->q); free(d->a); free(d->b); free(d);

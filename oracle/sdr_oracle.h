@@ -14,8 +14,9 @@
  * in DESIGN.md. The reference's own headers do compile over stand-ins for the
  * few library calls they make: ref_probe.cpp (windows, taps, quadrature) and
  * ref_blocks.cpp (the loops of this file among them: AGC, DC blocker,
- * de-emphasis) record their outputs in tests/golden/ref_*.npz, which
- * tests/test_ref_pinned.py and tests/test_ref_blocks.py hold this library to.
+ * de-emphasis, and the channel chain with its setters and resets) record their
+ * outputs in tests/golden/ref_*.npz, which tests/test_ref_pinned.py,
+ * tests/test_ref_blocks.py and tests/test_ref_chain.py hold this library to.
  *
  * Two accumulation modes for every dot product:
  *   precise=1  fp64 accumulation, rounded once to float (the parity truth)
@@ -67,6 +68,7 @@ enum { ORC_F32 = 0, ORC_C64 = 1 };
 typedef struct orc_fir orc_fir;
 orc_fir* orc_fir_create(int dtype, int ttype, const float* taps, int ntaps, int decim, int precise);
 void     orc_fir_set_taps(orc_fir* f, const float* taps, int ntaps);
+void     orc_fir_set_decimation(orc_fir* f, int decim);
 void     orc_fir_reset(orc_fir* f);
 int      orc_fir_process(orc_fir* f, const float* in, int count, float* out);
 void     orc_fir_destroy(orc_fir* f);
@@ -83,6 +85,7 @@ void orc_xlator_destroy(orc_xlator* x);
 typedef struct orc_quad orc_quad;
 orc_quad* orc_quad_create(double deviation_rad);
 void orc_quad_reset(orc_quad* q);
+void orc_quad_set_deviation(orc_quad* q, double deviation_rad);
 int  orc_quad_process(orc_quad* q, const float* in, int count, float* out);
 void orc_quad_destroy(orc_quad* q);
 
@@ -101,12 +104,15 @@ void orc_poly_destroy(orc_poly* p);
 typedef struct orc_rres orc_rres;            /* multirate/rational_resampler.h */
 orc_rres* orc_rres_create(int dtype, double inSr, double outSr, int precise);
 int  orc_rres_process(orc_rres* r, const float* in, int count, float* out);
+void orc_rres_reset(orc_rres* r);
 int  orc_rres_info(orc_rres* r, int* mode, int* predec, int* interp, int* decim, int* ntaps);
 void orc_rres_destroy(orc_rres* r);
 
 typedef struct orc_vfo orc_vfo;              /* channel/rx_vfo.h */
 orc_vfo* orc_vfo_create(double inSr, double outSr, double bw, double offset, int precise);
 int  orc_vfo_process(orc_vfo* v, const float* in, int count, float* out);
+void orc_vfo_set_offset(orc_vfo* v, double offset);
+void orc_vfo_reset(orc_vfo* v);
 void orc_vfo_destroy(orc_vfo* v);
 
 typedef struct orc_wfm orc_wfm;              /* demod/broadcast_fm.h (mono path) */
@@ -121,6 +127,7 @@ void orc_wfms_destroy(orc_wfms* w);
 typedef struct orc_fm orc_fm;                /* demod/fm.h */
 orc_fm* orc_fm_create(double samplerate, double bandwidth, int lowPass, int highPass, int precise);
 int  orc_fm_process(orc_fm* f, const float* in, int count, float* out_mono);
+void orc_fm_reset(orc_fm* f);
 void orc_fm_destroy(orc_fm* f);
 
 /* loops / IIRs: serial reference semantics */
@@ -176,6 +183,10 @@ void orc_vfo_signal_info(const float* line, int fftSize, double wholeBandwidth, 
 typedef struct orc_ddcfm orc_ddcfm;          /* C3: xlator -> DecimatingFIR -> Quadrature */
 orc_ddcfm* orc_ddcfm_create(double offsetRad, const float* taps, int ntaps, int decim, double deviationRad, int precise);
 int  orc_ddcfm_process(orc_ddcfm* d, const float* in, int count, float* out);
+void orc_ddcfm_set_taps(orc_ddcfm* d, const float* taps, int ntaps);
+void orc_ddcfm_set_decimation(orc_ddcfm* d, int decim);
+void orc_ddcfm_set_deviation(orc_ddcfm* d, double deviationRad);
+void orc_ddcfm_reset(orc_ddcfm* d);
 void orc_ddcfm_destroy(orc_ddcfm* d);
 
 /* recorder WAV encoders (utils/wav.cpp:296-336): kind 0 u8, 1 i16, 2 i24, 3 i32, 4 f32 */

@@ -113,6 +113,10 @@ class Quadrature(Block):
     def __init__(self, deviation_rad, device=0):
         super().__init__(_make(lib.sdrgpu_quadrature_create, device, float(deviation_rad)), np.complex64, np.float32)
 
+    def set_deviation(self, deviation_rad):
+        """setDeviation (demod/quadrature.h:29-33)."""
+        check(lib.sdrgpu_quadrature_set_deviation(self._h, float(deviation_rad)))
+
 
 class PowerDecimator(Block):
     """dsp::multirate::PowerDecimator<T> (multirate/power_decimator.h)."""
@@ -153,7 +157,20 @@ class RxVFO(Block):
         check(lib.sdrgpu_rxvfo_set_offset(self._h, float(offset)))
 
 
-class DDC(Block):
+class _FusedDDC(Block):
+    """The FIR stage's setters on a fused handle (sdrgpu_fir_set_taps / _set_decimation take it: the handle
+    is a FIR block with the xlator fused in)."""
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self._taps = t
+        check(lib.sdrgpu_fir_set_taps(self._h, _fptr(t), int(t.shape[0])))
+
+    def set_decimation(self, decim):
+        check(lib.sdrgpu_fir_set_decimation(self._h, int(decim)))
+
+
+class DDC(_FusedDDC):
     """Fused FrequencyXlator -> DecimatingFIR<complex_t,float> (complex out): the FIR stage of DDCFM."""
 
     def __init__(self, offset_rad, taps, decim, device=0):
@@ -163,7 +180,7 @@ class DDC(Block):
         super().__init__(h, np.complex64, np.complex64)
 
 
-class DDCFM(Block):
+class DDCFM(_FusedDDC):
     """Fused FrequencyXlator -> DecimatingFIR<complex_t,float> -> Quadrature (BASELINE config C3)."""
 
     def __init__(self, offset_rad, taps, decim, deviation_rad, device=0):
@@ -172,6 +189,9 @@ class DDCFM(Block):
         h = _make(lib.sdrgpu_ddc_fm_create, device, float(offset_rad), _fptr(t), int(t.shape[0]), int(decim),
                   float(deviation_rad))
         super().__init__(h, np.complex64, np.float32)
+
+    def set_deviation(self, deviation_rad):
+        check(lib.sdrgpu_quadrature_set_deviation(self._h, float(deviation_rad)))
 
 
 class FM(Block):

@@ -98,3 +98,31 @@ def test_measure_one_core_not_below_streams():
     assert r["value_1core"] >= r["value_1core_run"] and r["value_1core"] >= r["value_1core_spread_mean"]
     assert r["value_all_cores"] <= r["cores_all"] * r["value_1core"] * (1 + 1e-9), r
     assert r["value_1core_cpu"] in r["host"]["placement"]["cpus_spread"]
+
+
+def test_native_copy_is_this_checkouts(tmp_path, monkeypatch):
+    """The -march=native copy that the baseline's workers load lies in a directory every checkout on the host
+    shares. One left there by other sources, whatever its file time, must not be handed to this checkout's
+    oracle.py, which binds functions it may lack: the copy is named after its sources' contents, carries
+    every function oracle.py binds, and is built once."""
+    import ctypes
+    import os
+    import subprocess
+    import time
+    import cpu_baseline as cb
+    monkeypatch.setenv("TMPDIR", str(tmp_path))
+    d = tmp_path / "sdrgpu_cpu_baseline"
+    d.mkdir()
+    (tmp_path / "old.c").write_text("int orc_fir_reset(void) { return 0; }\n")
+    stale = d / "libsdr_oracle_native.so"      # another checkout's copy, newer than this checkout's sources
+    subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", str(stale), str(tmp_path / "old.c")])
+    os.utime(stale, (time.time() + 3600, time.time() + 3600))
+    so = cb.native_oracle()
+    assert so and so != str(stale) and os.path.dirname(so) == str(d)
+    L = ctypes.CDLL(so)
+    for name in ("orc_fir_set_decimation", "orc_vfo_set_offset", "orc_vfo_reset", "orc_ddcfm_set_taps", "orc_fm_reset",
+                 "orc_quad_set_deviation", "orc_rres_reset", "cf_chan_fir"):
+        assert hasattr(L, name), name
+    built = os.path.getmtime(so)
+    assert cb.native_oracle() == so and os.path.getmtime(so) == built
+    assert sorted(os.listdir(d)) == sorted([os.path.basename(so), stale.name])

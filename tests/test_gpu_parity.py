@@ -1022,14 +1022,15 @@ def test_spectrum_f64_zoom_rows(rng):
 
 
 # ------------------------------------------------- spectrum + VFO fused read
-def _fused_vs_separate(frames_list, pre, rng, zoom=False):
+def _fused_vs_separate(frames_list, pre, rng, zoom=False, between=None):
     """sdrgpu_fft_execute_vfo_dev / _zoom_vfo_dev (the VFO's first stage inside the spectrum launches)
     against the same batches through sdrgpu_fft_execute_dev / _zoom_dev + RxVFO.process_dev, and the
     VFO stream (ragged plain calls mixed with batch calls: non-zero decimation phase and history at a
     batch call) against the oracle. The fused launches run the same tile and segment code as the
     separate ones (only the cache policy of pass A's input loads and the stage's row batch differ,
     neither of which touches an output's arithmetic), so rows, zoom rows and VFO output are
-    bit-identical to the separate launches."""
+    bit-identical to the separate launches. `between` {k: (method, args...)}: a setter or reset issued on
+    both VFO handles and on the oracle's ahead of batch k."""
     import torch
     N, zw = 65536, 2048
     fs, off = 61.44e6, 2.5e6
@@ -1040,7 +1041,10 @@ def _fused_vs_separate(frames_list, pre, rng, zoom=False):
     if pre:   # a ragged plain call first: non-zero decimation phase and a history at the fused call
         x0 = iq(rng, pre)
         ya.append(fused_vfo.process(x0)); yb.append(sep_vfo.process(x0)); yo.append(ovfo.process(x0))
-    for frames in frames_list:
+    for k, frames in enumerate(frames_list):
+        if between and k in between:
+            for v in (fused_vfo, sep_vfo, ovfo):
+                getattr(v, between[k][0])(*between[k][1:])
         x = iq(rng, frames * N)
         d_x = torch.from_numpy(x.view(np.float32)).cuda()
         ra = torch.empty(frames * N, device="cuda")
@@ -1110,6 +1114,19 @@ def test_spectrum_vfo_fused_xcd(frames_list, pre, chunk_mb, rng, monkeypatch):
     if chunk_mb:
         monkeypatch.setenv("SDRGPU_FFT_CHUNK_MB", str(chunk_mb))
     _fused_vs_separate(frames_list, pre, rng, zoom=True)
+
+
+@pytest.mark.parametrize("plan", ["one-pass", "two-pass"])
+def test_spectrum_vfo_fused_retune_and_reset(plan, rng, monkeypatch):
+    """RxVFO::setOffset, then reset, between two-frame batches of the fused launches, after a ragged plain
+    call: set_offset rewrites the NCO tables of the VFO's fused first stage, which the spectrum launches
+    read themselves, and reset clears its history, decimation phase and NCO phase. Rows, zoom rows and
+    VFO output stay bit-identical to the separate launches given the same calls, and the VFO stream within
+    the bar of the oracle (pinned to the reference's setOffset and reset by test_ref_chain.py) given the
+    same calls, on the one-pass plan and on the two-pass plan."""
+    monkeypatch.setenv("SDRGPU_TUNING", "1")
+    monkeypatch.setenv("SDRGPU_FFT_1P", "1" if plan == "one-pass" else "0")
+    _fused_vs_separate([2, 2, 2], 1000, rng, zoom=True, between={1: ("set_offset", -1.5e6), 2: ("reset",)})
 
 
 # ------------------------------------------------- the one-pass 64k spectrum (fft_1p_kernel)

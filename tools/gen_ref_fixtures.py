@@ -7,7 +7,12 @@ tree) checks against them.
 * oracle/_ref/ref_blocks (and ref_blocks_sum4, the same with 4-lane summation order) -- the stateful
   blocks and chains: ref_blocks_*.npz, one file per group of blocks, each holding the seeded inputs,
   the parameters and the reference outputs. `blocks_fixtures()` builds them in memory;
-  tests/test_ref_blocks.py calls it to require that a fresh build reproduces the committed files."""
+  tests/test_ref_blocks.py calls it to require that a fresh build reproduces the committed files.
+* the same probe's channel-chain modes (and ref_blocks_rot64, the rotator's phase carried in fp64) --
+  FrequencyXlator, FIR / DecimatingFIR, PowerDecimator, the resamplers, RxVFO, Quadrature, FM and the
+  literal DDC chains with their setters and resets: ref_chain_*.npz, one file per case (two where the
+  arrays would exceed the size limit). `chain_fixtures()` builds them; tests/test_ref_chain.py holds
+  the C oracle and the device blocks to them and requires that a fresh build reproduces them."""
 import hashlib
 import os
 import subprocess
@@ -212,6 +217,148 @@ def blocks_fixtures():
     return files
 
 
+# ---------------------------------------------------------------- channel chain (ref_chain_*.npz)
+CHAIN_BUILDS = ("", "_sum4", "_rot64")   # ascending sums; 4-lane sums; the rotator's phase carried in fp64
+
+
+def chain_run(build, mode, ops, params, stdin, out_dtype, tail_dtype=None):
+    """One run of ref_blocks<build> over the op list `ops` (a comma string): (int32 counts per process()
+    call, outputs[, the ddcfm mode's FIR-stage outputs])."""
+    raw = subprocess.run([BLOCKS + build, mode, ops, *map(num, params)], input=stdin, capture_output=True, check=True).stdout
+    nc = int(np.frombuffer(raw[:4], np.int32)[0])
+    counts = np.frombuffer(raw[4:4 + 4 * nc], np.int32)
+    total, at = int(counts.sum()), 4 + 4 * nc
+    y = np.frombuffer(raw[at:at + total * np.dtype(out_dtype).itemsize], out_dtype)
+    rest = raw[at + y.nbytes:]
+    if tail_dtype is None:
+        assert not rest
+        return counts, y
+    z = np.frombuffer(rest, tail_dtype)
+    assert len(z) == total
+    return counts, y, z
+
+
+def cut_calls(n, small):
+    """`n` samples as calls: 1, 0, `small` (below the case's ntaps - 1), odd counts that no decimation of the
+    cases divides throughout, then what is left in two unequal calls."""
+    out = []
+    for c in (1, 0, small, 7, 0, 129, 1025):
+        if sum(out) + c > n:
+            break
+        out.append(c)
+    rest = n - sum(out)
+    return out + ([rest // 3, rest - rest // 3] if rest > 2 else [rest] if rest else [])
+
+
+def from_i16(k):
+    """Stored int16 samples -> float32 / complex64 (k [n] or [n, 2]), x = k / 32768: exact in fp32."""
+    x = (np.asarray(k, np.float32) / np.float32(32768.0)).astype(np.float32)
+    return np.ascontiguousarray(x).view(np.complex64)[:, 0] if x.ndim == 2 else x
+
+
+def noise_i16(seed, n, cplx):
+    return np.random.default_rng(seed).integers(-32768, 32768, (n, 2) if cplx else n).astype(np.int16)
+
+
+def fm_carrier_i16(seed, n, w0, dev, noise=0.0):
+    """A unit FM carrier at w0 rad/sample, its frequency deviating by dev * (a slow random tone mix), as int16 IQ."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n)
+    m = sum(np.sin(2 * np.pi * f * t + p) for f, p in zip(rng.uniform(0.001, 0.01, 3), rng.uniform(0, 6.28, 3))) / 3
+    x = 0.9 * np.exp(1j * (w0 * t + dev * np.cumsum(m)))
+    x = x + noise * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    return np.round(np.stack([x.real, x.imag], 1) * 32768).clip(-32768, 32767).astype(np.int16)
+
+
+def random_taps(seed, n, cplx=False, scale=1.0):
+    """+-[0.5, 1] * scale / n: no tap lies below the comparison bar, so a dropped or shifted tap shows."""
+    rng = np.random.default_rng(seed)
+    draw = lambda: rng.choice([-1.0, 1.0], n) * rng.uniform(0.5, 1.0, n) * scale / n
+    return (draw() + 1j * draw()).astype(np.complex64) if cplx else draw().astype(np.float32)
+
+
+def chain_cases():
+    """name -> (mode, params, tap sets, int16 input, op list, small, output dtype): every channel-chain case.
+    The op list holds sample counts (one segment each; the cut feed splits it with cut_calls) and op strings."""
+    f32, c64 = np.float32, np.complex64
+    C = {}
+    # FirBlock::select_kernel (complex data, real taps), segment by segment:
+    #   D = 8, 256 taps (32 per phase): fir_mfma_kernel
+    #   d32 (8 per phase): fir_rows_kernel at 8 taps per phase, from the MFMA tiles' history
+    #   t1: 143 taps (5 per phase): fir_rows_kernel at 5 taps per phase
+    #   t2 + d4: 27 taps (7 per phase): fir_mfma_ps_kernel, from the row kernel's history
+    #   d3 (not a power of two): the tile kernel, from the phase-split tiles' history
+    #   d1 (27 per phase): fir_mfma_kernel again, from the tile kernel's history; r; the same from zeros
+    C["fir_walk"] = ("fir_cf", [8], [random_taps(1, 256), random_taps(2, 143), random_taps(3, 27)], noise_i16(11, 16384, True),
+                     [4099, "d32", 4101, "t1", 3070, "t2", "d4", 2051, "d3", 1021, "d1", 1025, "r", 1017], 20, c64)
+    C["fir_real"] = ("fir_ff", [2], [random_taps(4, 69)], noise_i16(12, 4004, False), [1501, "d5", 1502, "r", 1001], 30, f32)
+    C["fir_cc"] = ("fir_cc", [1], [random_taps(5, 33, True), random_taps(6, 17, True), random_taps(7, 33, True)],
+                   noise_i16(13, 3002, True), [801, "t1", 800, "t2", 801, "r", 600], 11, c64)
+    C["xlator"] = ("xlator", [0.3], None, noise_i16(14, 16384, True), [5461, "w-0.7", 5461, "r", 5462], 20, c64)
+    C["quad"] = ("quad", [0.5], None, fm_carrier_i16(15, 3000, 0.1, 0.3, 0.05), [1000, "v0.2", 1000, "r", 1000], 20, f32)
+    for name, lp, hp in (("fm_lp", 1, 0), ("fm_bp", 1, 1)):
+        C[name] = ("fm", [48000.0, 12500.0, lp, hp], None, fm_carrier_i16(16, 4000, 0.05, 0.4, 0.02), [2501, "r", 1499], 20, f32)
+    w = -2 * np.pi * 0.11
+    C["ddc"] = ("ddc", [w, 8], [random_taps(8, 256), random_taps(9, 143)], noise_i16(17, 4096, True),
+                [1027, "t1", 1025, "d4", 1023, "r", 1021], 20, c64)
+    # ddcfm: low-passes whose last tap (the one the newest sample meets) alone passes a quarter of the carrier, so
+    # the FIR output keeps an envelope from the first sample after a reset; a small random part on every tap
+    geo = lambda seed, n: (0.3 * 0.7 ** np.arange(n)[::-1] + random_taps(seed, n, scale=0.25)).astype(f32)
+    C["ddcfm"] = ("ddcfm", [w, 8, 0.05], [geo(20, 256), geo(21, 143)], fm_carrier_i16(18, 8192, -w, 0.004),
+                  [2051, "t1", 2049, "d4", 1025, "v0.11", 1022, "r", 2045], 20, f32)
+    C["pdec_64_c"] = ("pdec_c", [64], None, noise_i16(30, 8192, True), [4133, "r", 4059], 20, c64)
+    C["pdec_64_f"] = ("pdec_f", [64], None, noise_i16(31, 8192, False), [4133, "r", 4059], 20, f32)
+    C["pdec_256_c"] = ("pdec_c", [256], None, noise_i16(32, 16384, True), [8229, "r", 8155], 20, c64)
+    for k, (interp, decim, nt) in enumerate([(3, 2, 100), (5, 4, 128), (1, 7, 45)]):
+        for t in ("f", "c"):
+            C[f"poly_{interp}_{decim}_{t}"] = (f"poly_{t}", [interp, decim], [random_taps(40 + k, nt, scale=interp)],
+                                               noise_i16(50 + k, 3000, t == "c"), [1501, "r", 1499], 9, c64 if t == "c" else f32)
+    C["rres_both"] = ("rres_c", [2.4e6, 48000.0], None, noise_i16(60, 32768, True), [16421, "r", 16347], 20, c64)
+    C["rres_decim"] = ("rres_c", [3.84e6, 60000.0], None, noise_i16(61, 8192, True), [4133, "r", 4059], 20, c64)
+    C["rres_resamp"] = ("rres_f", [48000.0, 44100.0], None, noise_i16(62, 4000, False), [2501, "r", 1499], 20, f32)
+    C["rres_none"] = ("rres_c", [48000.0, 48000.0], None, noise_i16(63, 1000, True), [501, "r", 499], 20, c64)
+    # RxVFO: a fused first stage at D = 8 without LPF; the C5 shape (row kernel, three-stage tail, LPF);
+    # the xlator as its own kid ahead of the polyphase block
+    C["rxvfo_d64"] = ("rxvfo", [3.84e6, 60000.0, 60000.0, 1.7e5], None, noise_i16(70, 16384, True),
+                      [5461, "f-410000", 5461, "r", 5462], 20, c64)
+    C["rxvfo_c5"] = ("rxvfo", [61.44e6, 240000.0, 200000.0, 2.5e6], None, noise_i16(71, 102400, True),
+                     [34133, "f-1500000", 34133, "r", 34134], 20, c64)
+    C["rxvfo_poly"] = ("rxvfo", [48000.0, 44100.0, 40000.0, 3000.0], None, noise_i16(72, 4000, True),
+                       [1501, "f-5000", 1500, "r", 999], 20, c64)
+    return C
+
+
+def chain_fixtures():
+    """{file name: {key: array}} of every ref_chain_*.npz: per case the int16 input, parameters, tap sets, both op
+    lists (the segments whole, and in cuts) and per feed and build the per-call counts and outputs."""
+    files = {}
+    for name, (mode, params, taps, xi, segs, small, dt) in chain_cases().items():
+        x = from_i16(xi)
+        stdin = b""
+        if taps is not None:
+            stdin = np.int32(len(taps)).tobytes() + b"".join(np.int32(len(t)).tobytes() + t.tobytes() for t in taps)
+        stdin += x.tobytes()
+        assert sum(s for s in segs if not isinstance(s, str)) == len(x), name
+        g = {"mode": np.array(mode), "params": np.array(params, np.float64), "xi16": xi}
+        for k, t in enumerate(taps or []):
+            g[f"taps{k}"] = t
+        feeds = {"whole": ",".join(map(str, segs)),
+                 "cut": ",".join(s if isinstance(s, str) else ",".join(map(str, cut_calls(s, small))) for s in segs)}
+        for feed, ops in feeds.items():
+            g[f"ops_{feed}"] = np.array(ops)
+            for build in CHAIN_BUILDS:
+                r = chain_run(build, mode, ops, params, stdin, dt, np.complex64 if mode == "ddcfm" else None)
+                g[f"{feed}_counts{build}"], g[f"{feed}_y{build}"] = r[0], r[1]
+                if mode == "ddcfm":
+                    g[f"{feed}_z{build}"] = r[2]
+        # incompressible noise: a case whose arrays exceed the size limit keeps the cut feed's outputs in a second file
+        if sum(v.nbytes for v in g.values()) > MAX_BYTES - 40000:
+            cut = {k: g.pop(k) for k in [k for k in g if k.startswith("cut_y") or k.startswith("cut_z")]}
+            files[f"ref_chain_{name}_cut.npz"] = cut
+        files[f"ref_chain_{name}.npz"] = g
+    return files
+
+
 # Known-answer signals of the chain fixtures: the seed of shaped_psk / gfsk_signal, (f0, snr_db, seed) of
 # rds_signal. tests/test_ref_blocks.py test_chain_inputs_meet_the_preconditions states the conditions they
 # are chosen to meet (both builds decide alike, no symbol within the comparison bar of a decision boundary,
@@ -247,7 +394,7 @@ def main():
     offs = np.array([2 * np.pi * (-1.5e6 / 61.44e6), 2 * np.pi * (-2.5e6 / 61.44e6), 2 * np.pi * (2.5e6 / 61.44e6)])
     deltas = np.stack([np.frombuffer(probe("xlatordelta", f"{float(o):.17g}"), np.float32) for o in offs])
     np.savez_compressed(os.path.join(OUT, "ref_quad.npz"), x=x, dev=dev, y=y, offs=offs, deltas=deltas)
-    for fname, arrays in blocks_fixtures().items():
+    for fname, arrays in {**blocks_fixtures(), **chain_fixtures()}.items():
         path = os.path.join(OUT, fname)
         np.savez_compressed(path, **arrays)
         size = os.path.getsize(path)
