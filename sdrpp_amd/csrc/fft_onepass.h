@@ -38,7 +38,8 @@ constexpr int RS = 560;                 // LDS row stride (float2)
 constexpr int TW512 = 32 * RS;          // W_512^(t0 q1) at [q1][t0]
 constexpr int W128 = TW512 + 512;       // W_128^(r i), i < 32
 constexpr int W128D = (W128 + 64) * 8;   // (bytes) fp64 W_128^(r i), r = r0, r0 + 1, i < 32
-constexpr int LDS_BYTES = W128D + 64 * 16;
+constexpr int PHI = W128D + 64 * 16;    // (bytes) the walk's coarse NCO phasors of the fused VFO, 512 float2
+constexpr int LDS_BYTES = PHI + 512 * 8;
 constexpr int TAB = 512 + 128;          // device table: [q1][t0] W_512^(t0 q1), [r][i] W_128^(r i)
 constexpr int TAB64 = 2048 + 128;       // fp64 table: W_N^m (m < 2048), [r][i] W_128^(r i)
 }
@@ -84,7 +85,10 @@ constexpr int k1pPB = 2;   // (PAD) sample rows per load batch: 4 PB loads of x 
 #ifndef SDRGPU_1P_ABL
 #define SDRGPU_1P_ABL 0   // (ablation builds, wrong results, timing only) 1: no loads, 2: no transforms, 4: no VFO,
                           // 8: fp32 stage-1 twiddles, 16: no dB / stores (32, round 15 only: the shared row ring without
-                          // its 32 barriers, group 1.449 -> 1.383 ms, the ceiling of the wave-private ring; profiles/r15)
+                          // its 32 barriers, group 1.449 -> 1.383 ms, the ceiling of the wave-private ring; profiles/r15),
+                          // 64: the VFO half's round 0 reads the same rows of a fixed frame of the call (hot in L2: the
+                          // ceiling of warming round 0's lines), 128: the VFO segments' coarse phasor a constant (the
+                          // ceiling of forming it outside the walk); profiles/r20
 #endif
 // Decided A/Bs, kept forms only: the ring's first k1pSlots - 1 row sets are issued before the VFO half, so they
 // land while it computes (C5 group 1.518 -> 1.499 ms, same bits, r6g); quarter r0 + 1's W_128 products run
@@ -93,6 +97,9 @@ constexpr int k1pPB = 2;   // (PAD) sample rows per load batch: 4 PB loads of x 
 // loop (C5 group 1.451 -> 1.419 ms, same bits; recomputed per row set 1.427-1.439 ms; r15c, r15d). Measured and not
 // kept (profiles/r15): stage 2 without the barrier between its reads and writes, which orders nothing across waves
 // (1.435 vs 1.448 and 1.435 vs 1.421 ms alone, 1.409 vs 1.419 ms beside the ring: inside the run-to-run spread).
+// Round 20 (profiles/r20): the VFO segments' coarse NCO phasors come from an LDS table formed once per launch
+// (C5 group 1.418 -> 1.397 and 1.398 -> 1.366 ms, same bits, r20f, r20g). Measured and not kept: the next item's VFO
+// round-0 lines touched from the prefetch (1.472 ms at a 128-B lane stride, 1.485 ms at 64 B, vs 1.447 ms, r20c).
 #ifdef SDRGPU_1P_TIMING   // (measurement builds) per-item phase stamps of wave 0: slots 0-7 and 9 (the first
                           // ring wait) s_memtime; slot 8 the CU's identity, XCC_ID << 32 | HW_ID
 constexpr int k1pStamps = 10;
@@ -115,15 +122,55 @@ __device__ unsigned long long g_1p_t[16384 * k1pStamps];
 #define T1P_CU(item) do {} while (0)
 #endif
 #define T1P(k) T1P_AT(b, k)
+struct NcoPhiConst {   // (ablation 128)
+    __device__ __forceinline__ float2 operator()(const FirArgs&, long long) const { return make_float2(0.6f, 0.8f); }
+};
+// The VFO half's geometry as the walk needs it: item (frame g, quarter pair p) runs the segments
+// 64 (frame0 + g) + 32 p .. + 31 (vfo_half_block), segment s starts at input index offset0 - H + 32 * 32 s
+// (fir_rows_segment: RS = 32 outputs of the D = 32 decimator) and forms its phasor at its first 32 samples.
+namespace op1 {
+constexpr int VSEG = 32 * 32;   // a segment's step in input samples
+// coarse indices (nco_value.h: input index >> NCO_LO_BITS, an arithmetic shift: the floor, inside the history
+// too) an item's 32 segment starts can take: the starts span 31 VSEG + 32 samples
+constexpr int PHI_E = ((31 * VSEG + 31) >> NCO_LO_BITS) + 2;
+constexpr int PHI_ITEMS = 512 / PHI_E;   // items of a walk the table holds (one entry per thread of the prologue)
+// coarse index of an item's first entry
+__device__ __forceinline__ long long vfo_item_j0(const FirArgs& a, int frame0, int g, int p) {
+    return ((long long)a.offset0 - a.H + ((long long)(frame0 + g) * 64 + p * 32) * VSEG) >> NCO_LO_BITS;
+}
+}
+// The coarse phasors of an item from the workgroup's LDS table (fft_1p_kernel's prologue), or formed in place for
+// the items of a walk beyond the table (workgroup-uniform)
+struct NcoPhiLds {
+    unsigned base;   // LDS byte address of the item's entry of coarse index 0 (entries of 8 bytes; modulo 2^32)
+    bool tab;
+    __device__ __forceinline__ float2 operator()(const FirArgs& a, long long j) const {
+        if (tab) {
+            const auto* e = (const __attribute__((address_space(3))) float*)(size_t)(base + 8u * (unsigned)j);
+            return make_float2(e[0], e[1]);
+        }
+        return nco_phi(a.ncoTheta0, a.ncoW, j);
+    }
+};
 // (the quarter pair of a workgroup: its VFO share, 32 segments of the frame's 64)
-__device__ __forceinline__ void vfo_half_block(const VfoWork& v, int g, int p) {
+template <class PHI = NcoPhiInline>
+__device__ __forceinline__ void vfo_half_block(const VfoWork& v, int g, int p, const PHI& coarse = PHI{}) {
     int u = threadIdx.x;
     asm volatile("" : "+v"(u));   // (laundered: nothing of a segment's addressing is hoisted out of the item walk)
     const int lane = u & 63, wave = u >> 6;
 #pragma unroll 1
     for (int k = 0; k < 2; k++) {
         const long long seg = (long long)(v.frame0 + g) * 64 + p * 32 + k * 16 + wave * 2 + (lane >> 5);
-        fir_rows_segment<32, 5, true, false, 32, 32, true>(v.a, seg, lane);
+#if SDRGPU_1P_ABL & 64
+        // round 0 from frame 1 of the call, which every workgroup reads: the same offsets in the frame (frame 0
+        // would put the first segment's halo in front of the buffer)
+        FirArgs a = v.a;
+        if (k == 0 && v.frame0 + g > 1) a.in = reinterpret_cast<const float2*>(a.in) - (long long)(v.frame0 + g - 1) * 65536;
+#else
+        const FirArgs& a = v.a;
+#endif
+        if constexpr (SDRGPU_1P_ABL & 128) fir_rows_segment<32, 5, true, false, 32, 32, true>(a, seg, lane, NcoPhiConst{});
+        else fir_rows_segment<32, 5, true, false, 32, 32, true>(a, seg, lane, coarse);
     }
 }
 // (one struct, at offset 0 of the kernel's argument segment: every item of the walk reads what it needs of it
@@ -163,6 +210,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
     int p = (blockIdx.x >> 3) & 1;
     constexpr bool kDma = !PAD && !(SDRGPU_1P_ABL & 1);   // whole frames: the LDS-DMA row ring below
     constexpr bool kVfo = VFO && !(SDRGPU_1P_ABL & 4);
+    constexpr bool kTab = kVfo && kDma && !(SDRGPU_1P_ABL & 128);   // the coarse-phasor table (below)
     // Index arithmetic is recomputed from a laundered thread index where it is used: left alone, the
     // compiler hoists the loop-invariant load / LDS / store addresses and spills them.
     auto tid = [] {
@@ -174,6 +222,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
         const int t = threadIdx.x;
         lds[TW512 + t] = ka.tab[t];
         if (t < 64) reinterpret_cast<double2*>(reinterpret_cast<char*>(lds) + op1::W128D)[t] = ka.tab64[2048 + 32 * (2 * p + (t >> 5)) + (t & 31)];
+        // The VFO segments' coarse NCO phasors (nco_phi: an fp64 division, rint and sincos) depend on the call and
+        // the item's frame only, and an item's 32 segments take at most PHI_E of them: thread t forms entry t % PHI_E
+        // of item t / PHI_E of this workgroup's walk, once per launch, instead of every wave forming its own twice
+        // per item (the same expression, so the same bits; round 20, profiles/r20/README.md).
+        if constexpr (kTab) {
+            const int n = t / op1::PHI_E, bn = (int)blockIdx.x + n * G;
+            if (n < op1::PHI_ITEMS && bn < items)
+                reinterpret_cast<float2*>(reinterpret_cast<char*>(lds) + op1::PHI)[t] =
+                    nco_phi(ka.v.a.ncoTheta0, ka.v.a.ncoW,
+                            op1::vfo_item_j0(ka.v.a, ka.v.frame0, 8 * (bn >> 4) + (bn & 7), p) + (t - n * op1::PHI_E));
+        }
     }
     __syncthreads();   // (the tables staged: an item's W_128 products read them in front of its first barrier)
     const unsigned lim = PAD ? (unsigned)ka.nz : 65536u;     // (PAD: range-checked loads, 0 past nz)
@@ -239,8 +298,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
     // barrier of their own), the next item's first S - 1 row sets are issued into the ring, so they fly
     // under this item's last dft16, dB and store burst instead of behind the next item's first instruction.
     bool pre = false;   // (workgroup-uniform) this item's first S - 1 row sets were issued by the previous item
+    int nItem = 0;      // the item's place in the walk: its entries of the coarse-phasor table
 #pragma unroll 1
-    for (int b = blockIdx.x; b < items; b += G) {
+    for (int b = blockIdx.x; b < items; b += G, nItem++) {
         // (per-item index math from laundered values, the workgroup's constants included: left alone, the compiler
         // hoists what the items share out of the walk -- the ring's 96 slot addresses, the VFO segments' and the
         // image's addressing -- and spills it)
@@ -336,7 +396,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
                 set_rows(in + (long long)f * frameStride, win);
                 static_for<0, S - 1>(dma);
             }
-            if constexpr (kVfo) vfo_half_block(v, f, p);   // (its loads wait behind the ring's)
+            // (the VFO half: its loads wait behind the ring's)
+            if constexpr (kTab) {   // the segments' coarse phasors from the prologue's table; past its items, in place
+                const NcoPhiLds coarse{(unsigned)(size_t)l3 + (unsigned)op1::PHI +
+                                           8u * ((unsigned)(nItem * op1::PHI_E) - (unsigned)op1::vfo_item_j0(v.a, v.frame0, f, p)),
+                                       nItem < op1::PHI_ITEMS};
+                vfo_half_block(v, f, p, coarse);
+            } else if constexpr (kVfo) {
+                vfo_half_block(v, f, p);
+            }
             // The loop's counted waits take this wave's vmcnt to hold nothing but the row sets younger than the
             // one waited for. Behind a prefetch it also holds the previous item's dB and zoom stores, issued after
             // the prefetched row sets, and loads and stores do not retire in order relative to each other: a count
@@ -398,6 +466,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void f
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 set_rows(in + (long long)fn * frameStride, win);
                 static_for<0, S - 1>(dma);
+                // (Measured and not kept, round 20: every wave touching the lines of the next item's VFO round 0 here,
+                // as 4-byte LDS-DMAs one line per lane into a region nobody reads: C5 group +1.7 % at a 128-B lane
+                // stride, +2.6 % at 64 B; the round-0 loads from a frame hot in L2 were worth 0.1-0.4 % at most)
             }
         };
         auto transform = [&](auto hc, float2 (&z)[32]) {

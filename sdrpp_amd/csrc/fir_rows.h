@@ -92,6 +92,12 @@ struct FirArgs {
 __device__ __forceinline__ float2 nco_inline(const FirArgs& a, long long i) {
     return cmulf(nco_phi(a.ncoTheta0, a.ncoW, i >> NCO_LO_BITS), a.plo[i & (NCO_LO - 1)]);
 }
+// Where a row segment's coarse phasor comes from (fir_rows_segment's last argument): formed in place, the
+// default; the one-pass spectrum kernel passes a source of its own (fft_onepass.h). Any source returns
+// nco_phi(a.ncoTheta0, a.ncoW, j) to the bit.
+struct NcoPhiInline {
+    __device__ __forceinline__ float2 operator()(const FirArgs& a, long long j) const { return nco_phi(a.ncoTheta0, a.ncoW, j); }
+};
 template <bool TAB = true>   // TAB: read the per-call table; else form the coarse phasor in place
 __device__ __forceinline__ float2 nco_at(const FirArgs& a, long long i) {
     if constexpr (TAB) return nco_tab(a.phi, a.plo, i);
@@ -173,8 +179,8 @@ template <int D> constexpr int rows_rs() { return D == 32 ? 128 : 256; }
 // does not spill the swizzle temporaries the scheduler would otherwise hoist (same instructions, same
 // bits).
 template <int D, int QP, bool XL, bool QUAD, int RS = rows_rs<D>(), int BT0 = (QP > 16 ? 16 : (D == 32 ? 64 : 32)),
-          bool LOWREG = false>
-__device__ __forceinline__ void fir_rows_segment(const FirArgs& a, long long seg, int lane) {
+          bool LOWREG = false, class PHI = NcoPhiInline>
+__device__ __forceinline__ void fir_rows_segment(const FirArgs& a, long long seg, int lane, const PHI& coarse = PHI{}) {
     constexpr int QOFF = QUAD ? 1 : 0;
     // short segments (small calls) take one batch of RS rows
     constexpr int BT = BT0 < RS ? BT0 : RS;
@@ -195,7 +201,11 @@ __device__ __forceinline__ void fir_rows_segment(const FirArgs& a, long long seg
     const __attribute__((address_space(4))) float* nstep = (const __attribute__((address_space(4))) float*)a.nstep;
     // phasor of the segment's first input sample (index b0 - H + p of `in`; negative inside the
     // history, where the formula still holds: coarse index floor(i / 4096), fine index i mod 4096)
-    if constexpr (XL) ph0 = nco_inline(a, b0 - a.H + p);
+    // (nco_inline's expression, the coarse factor from `coarse`)
+    if constexpr (XL) {
+        const long long i0 = b0 - a.H + p;
+        ph0 = cmulf(coarse(a, i0 >> NCO_LO_BITS), a.plo[i0 & (NCO_LO - 1)]);
+    }
     float2* __restrict__ out2 = reinterpret_cast<float2*>(a.out);
     float* __restrict__ outf = reinterpret_cast<float*>(a.out);
     // interior segments load unconditionally (BT row loads in flight); the few segments touching
