@@ -292,6 +292,27 @@ int sdrgpu_costas_create(sdrgpu_block** h, int device, int order, double bandwid
                          double minFreq, double maxFreq);
 int sdrgpu_costas_set_bandwidth(sdrgpu_block* h, double bandwidth);                  /* pll.h:27 */
 int sdrgpu_costas_set_freq_limits(sdrgpu_block* h, double minFreq, double maxFreq);   /* pll.h:49: clamps freq at the next call */
+/* loop::PLL (loop/pll.h:15-25, 64-70) and loop::CarrierTrackingPLL (loop/carrier_tracking_pll.h:14-20); C64 -> C64.
+ * Per sample, PLL emits phasor(phase) taken before the advance and CarrierTrackingPLL the input derotated by
+ * it; both advance by normalizePhase(atan2f(in.im, in.re) - phase) of the INPUT sample. Arguments in
+ * PLL::init's order (pll.h:15) -- the constructors of PLL, CarrierTrackingPLL and MeteorCostas pass
+ * (initFreq, initPhase) swapped to it (pll.h:13, carrier_tracking_pll.h:10-12, meteor_costas.h:11): a port of
+ * code that constructs them swaps the two. The coefficients, reset and the refusals of sdrgpu_costas_create
+ * (but for its order); atan2f, cosf and sinf are the device libm's, so outputs follow the reference within
+ * the loop's own sensitivity. sdrgpu_costas_set_bandwidth and sdrgpu_costas_set_freq_limits are
+ * the setBandwidth (pll.h:27) and setFrequencyLimits (pll.h:49) of these two loops and of MeteorCostas as well. */
+int sdrgpu_pll_create(sdrgpu_block** h, int device, double bandwidth, double initPhase, double initFreq, double minFreq,
+                      double maxFreq);
+int sdrgpu_carrier_pll_create(sdrgpu_block** h, int device, double bandwidth, double initPhase, double initFreq, double minFreq,
+                              double maxFreq);
+/* loop::MeteorCostas (decoder_modules/meteor_demodulator/src/meteor_costas.h:13-16, 24-56); C64 -> C64; arguments in
+ * its init's order (:13). With brokenModulation 0 the error is Costas<4>'s (:53) and the block is bit-identical
+ * to sdrgpu_costas_create(order 4); else the error is the distance of the derotated sample's atan2f phase to the
+ * nearest of PHASE1..4 (:36-49), times its amplitude, clamped to [-1, 1]. set_broken_modulation (:18-22) applies
+ * from the next call and keeps the loop state; it also takes a Meteor handle. */
+int sdrgpu_meteor_costas_create(sdrgpu_block** h, int device, double bandwidth, int brokenModulation, double initPhase,
+                                double initFreq, double minFreq, double maxFreq);
+int sdrgpu_meteor_costas_set_broken_modulation(sdrgpu_block* h, int enabled);
 /* clock_recovery::MM<T> (clock_recovery/mm.h:24-156); dtype F32 or C64. Output count and every
  * output are bit-identical to the reference arithmetic with these definitions / deviations:
  *  - the interpolator dot product (volk_32f_x2_dot_prod_32f / volk_32fc_32f_dot_prod_32fc, whose SIMD
@@ -321,6 +342,23 @@ int sdrgpu_differential_decoder_create(sdrgpu_block** h, int device, int modulus
 int sdrgpu_psk_create(sdrgpu_block** h, int device, int order, double symbolrate, double samplerate, int rrcTapCount,
                       double rrcBeta, double agcRate, double costasBandwidth, double omegaGain, double muGain,
                       double omegaRelLimit);
+/* demod::Meteor, the LRPT demodulator (decoder_modules/meteor_demodulator/src/meteor_demod.h:24-43, 150-167;
+ * main.cpp:66 creates it as init(in, 72000, 150000, 33, 0.6, 0.1, 0.005, broken, oqpsk, 1e-6, 0.01)):
+ * FIR(rootRaisedCosine) -> FastAGC(1, 10e6, agcRate) -> MeteorCostas(costasBandwidth, brokenModulation) -> with
+ * oqpsk, the one-sample I/Q stagger of :155-164 -> MM<complex_t>(samplerate / symbolrate, ...); C64 -> C64
+ * symbols. Arguments in init's order (:24). The RRC FIR sums as the stream banks' FIR does (ascending tap order, fp32,
+ * no contraction: VOLK's generic kernel), not as sdrgpu_fir_create: the chain then differs from the reference by the
+ * loop's libm alone, and a column of sdrgpu_bank_meteor_create is this chain bit for bit. The stagger runs in the loop's kernel; its carry lastI (:188) lives on
+ * the device, starts at 0, is carried across calls (empty ones too), is updated only while oqpsk is on, keeps
+ * its value while it is off, and reset (:139-148: the four blocks) does not touch it. The refusals of
+ * sdrgpu_psk_create, all before the device is selected; count and capacity as sdrgpu_mm_create (the return
+ * value is the exact count; the call waits once). set_broken_modulation (:127) and set_oqpsk (:133) apply from
+ * the next call. sdrgpu_mm_set_*, sdrgpu_fast_agc_set and sdrgpu_costas_set_bandwidth reach its blocks. */
+int sdrgpu_meteor_create(sdrgpu_block** h, int device, double symbolrate, double samplerate, int rrcTapCount, double rrcBeta,
+                         double agcRate, double costasBandwidth, int brokenModulation, int oqpsk, double omegaGain,
+                         double muGain, double omegaRelLimit);
+int sdrgpu_meteor_set_broken_modulation(sdrgpu_block* h, int enabled);
+int sdrgpu_meteor_set_oqpsk(sdrgpu_block* h, int enabled);
 /* demod::GFSK (demod/gfsk.h:24-41, 131-135): Quadrature(deviation) -> FIR(rootRaisedCosine) ->
  * MM<float>; C64 -> F32 soft symbols */
 int sdrgpu_gfsk_create(sdrgpu_block** h, int device, double symbolrate, double samplerate, double deviation, int rrcTapCount,
@@ -384,6 +422,21 @@ int sdrgpu_bank_mm_create(sdrgpu_bank** h, int device, int streams, int dtype, d
 int sdrgpu_bank_psk_create(sdrgpu_bank** h, int device, int streams, int order, double symbolrate, double samplerate,
                            int rrcTapCount, double rrcBeta, double agcRate, double costasBandwidth, double omegaGain,
                            double muGain, double omegaRelLimit);
+/* loop::PLL, loop::CarrierTrackingPLL and loop::MeteorCostas per stream (loop/pll.h:64-70,
+ * loop/carrier_tracking_pll.h:14-20, decoder_modules/meteor_demodulator/src/meteor_costas.h:24-56); the arguments and
+ * refusals of the single-stream create functions; every column bit-identical to them on the same device */
+int sdrgpu_bank_pll_create(sdrgpu_bank** h, int device, int streams, double bandwidth, double initPhase, double initFreq,
+                           double minFreq, double maxFreq);
+int sdrgpu_bank_carrier_pll_create(sdrgpu_bank** h, int device, int streams, double bandwidth, double initPhase, double initFreq,
+                                   double minFreq, double maxFreq);
+int sdrgpu_bank_meteor_costas_create(sdrgpu_bank** h, int device, int streams, double bandwidth, int brokenModulation,
+                                     double initPhase, double initFreq, double minFreq, double maxFreq);
+/* demod::Meteor per stream (meteor_demod.h:24-43, 150-167): bank FIR(rootRaisedCosine) -> bank FastAGC(1, 10e6,
+ * agcRate) -> bank MeteorCostas with the per-stream stagger (lastI[S], kept by reset) -> bank MM<complex_t>, the
+ * constants of sdrgpu_meteor_create; bit-identical to those banks run one after another; counts as the MM bank */
+int sdrgpu_bank_meteor_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate, int rrcTapCount,
+                              double rrcBeta, double agcRate, double costasBandwidth, int brokenModulation, int oqpsk,
+                              double omegaGain, double muGain, double omegaRelLimit);
 /* demod::GFSK per stream (demod/gfsk.h:24-41, 131-135): bank Quadrature(deviation) -> bank
  * FIR(rootRaisedCosine) -> bank MM<float>; C64 -> F32 soft symbols */
 int sdrgpu_bank_gfsk_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate, double deviation,

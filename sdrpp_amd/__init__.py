@@ -160,6 +160,17 @@ def _load():
         "sdrgpu_costas_create": (i, [pp, i, i, d, d, d, d, d]),
         "sdrgpu_costas_set_bandwidth": (i, [vp, d]),
         "sdrgpu_costas_set_freq_limits": (i, [vp, d, d]),
+        "sdrgpu_pll_create": (i, [pp, i, d, d, d, d, d]),
+        "sdrgpu_carrier_pll_create": (i, [pp, i, d, d, d, d, d]),
+        "sdrgpu_meteor_costas_create": (i, [pp, i, d, i, d, d, d, d]),
+        "sdrgpu_meteor_costas_set_broken_modulation": (i, [vp, i]),
+        "sdrgpu_meteor_create": (i, [pp, i, d, d, i, d, d, d, i, i, d, d, d]),
+        "sdrgpu_meteor_set_broken_modulation": (i, [vp, i]),
+        "sdrgpu_meteor_set_oqpsk": (i, [vp, i]),
+        "sdrgpu_bank_pll_create": (i, [pp, i, i, d, d, d, d, d]),
+        "sdrgpu_bank_carrier_pll_create": (i, [pp, i, i, d, d, d, d, d]),
+        "sdrgpu_bank_meteor_costas_create": (i, [pp, i, i, d, i, d, d, d, d]),
+        "sdrgpu_bank_meteor_create": (i, [pp, i, i, d, d, i, d, d, d, i, i, d, d, d]),
         "sdrgpu_mm_create": (i, [pp, i, i, d, d, d, d, i, i]),
         "sdrgpu_mm_set_omega": (i, [vp, d]),
         "sdrgpu_mm_set_gains": (i, [vp, d, d]),

@@ -3,6 +3,7 @@
 // parameters, element m of stream k at x[m * S + k], one launch per block and call.
 //   BankQuad, BankFir        demod::Quadrature, filter::FIR<D, float> per stream
 //   BankFastAgc, BankCostas, BankMm   loop::FastAGC<T>, loop::Costas<ORDER>, clock_recovery::MM<T> per stream
+//   BankPll                  loop::PLL, loop::CarrierTrackingPLL, loop::MeteorCostas (with demod::Meteor's stagger) per stream
 //   BankAgc, BankDcb, BankDeemp      loop::AGC<T>, correction::DCBlocker<T>, filter::Deemphasis<float> per stream
 //   BankSquelch, BankMag     noise_reduction::Squelch per stream; volk_32fc_magnitude_32f over the flat stream
 //   BankXlator               channel::FrequencyXlator per stream on the single-stream NCO; also as translate -> real part
@@ -10,7 +11,7 @@
 //                            (bank_rate_kernels.h); the copy of a ratio of 1
 //   BankCfir, BankStereoDec, BankMonoPairs   filter::FIR<complex_t, complex_t> per stream; the stereo decoder of
 //                            demod::BroadcastFM (pilot filter -> PLL -> matrix) and its mono -> pairs (bank_wfm_kernels.h)
-//   BankChain                demod::PSK<ORDER> / demod::GFSK per stream (the constants of symsync.hip),
+//   BankChain                demod::PSK<ORDER> / demod::GFSK / demod::Meteor per stream (the constants of symsync.hip),
 //                            demod::FM<float> / demod::AM<float> / demod::SSB<float> / demod::CW<float> per stream
 //                            (those of blocks.hip / loops.hip), demod::BroadcastFM per stream (those of loops.hip),
 //                            multirate::PowerDecimator<T> / multirate::RationalResampler<T> per stream
@@ -222,6 +223,40 @@ struct BankCostas : Bank {
         if (order == 2) run_t<2>(in, frames, out, s);
         else if (order == 4) run_t<4>(in, frames, out, s);
         else run_t<8>(in, frames, out, s);
+        SDRGPU_HIP(hipGetLastError());
+        return frames;
+    }
+};
+
+// ---------------------------------------- MeteorCostas, PLL, CarrierTrackingPLL
+// the three other PLLs of the reference on BankCostas's configuration and state
+enum class PllKind { Meteor, Pll, Carrier };
+struct BankPll : BankCostas {
+    PllKind kind = PllKind::Pll;
+    int broken = 0, oqpsk = 0;
+    DevBuf lastI;   // lastI[S], demod::Meteor's stagger carry per stream: 0 at create, a reset keeps it
+    int configure(int streams, PllKind kind_, double bandwidth, int broken_, int oqpsk_, double initPhase_, double initFreq_,
+                  double minFreq, double maxFreq) {
+        kind = kind_;
+        broken = broken_ ? 1 : 0;
+        oqpsk = oqpsk_ ? 1 : 0;
+        return BankCostas::configure(streams, 4, bandwidth, initPhase_, initFreq_, minFreq, maxFreq);
+    }
+    int init() override {
+        if (kind == PllKind::Meteor) SDRGPU_CHECK(upload(lastI, std::vector<float>(S, 0.0f)));
+        return reset();
+    }
+    int run(const void* in, int frames, void* out, hipStream_t s) override {
+        if (frames == 0) return 0;
+        if (kind == PllKind::Meteor)
+            hipLaunchKernelGGL(bank_meteor_costas_kernel, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S, p,
+                               broken, oqpsk, state.as<float>(), lastI.as<float>());
+        else if (kind == PllKind::Carrier)
+            hipLaunchKernelGGL(bank_carrier_pll_kernel<true>, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S,
+                               pll_params(p), state.as<float>());
+        else
+            hipLaunchKernelGGL(bank_carrier_pll_kernel<false>, waves_of(S), dim3(BANK_W), 0, s, (const float2*)in, (float2*)out, frames, S,
+                               pll_params(p), state.as<float>());
         SDRGPU_HIP(hipGetLastError());
         return frames;
     }
@@ -928,6 +963,51 @@ extern "C" int sdrgpu_bank_psk_create(sdrgpu_bank** h, int device, int streams, 
     if (rc >= 0) { auto* a = new BankFastAgc(); rc = c->add(a, a->configure(streams, SDRGPU_C64, 1.0, 10e6, agcRate, 1.0)); }
     const double PI = 3.1415926535f;   // FL_M_PI, the default frequency limits (pll.h:15)
     if (rc >= 0) { auto* l = new BankCostas(); rc = c->add(l, l->configure(streams, order, costasBandwidth, 0.0, 0.0, -PI, PI)); }
+    if (rc >= 0) {
+        auto* m = new BankMm();
+        rc = c->add(m, m->configure(streams, SDRGPU_C64, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8));
+    }
+    return publish_bank(h, c, device, rc);
+}
+
+extern "C" int sdrgpu_bank_pll_create(sdrgpu_bank** h, int device, int streams, double bandwidth, double initPhase, double initFreq,
+                                      double minFreq, double maxFreq) {
+    NEED_BANK_OUT(h, "bank_pll_create");
+    auto* c = new BankPll();
+    return publish_bank(h, c, device, c->configure(streams, PllKind::Pll, bandwidth, 0, 0, initPhase, initFreq, minFreq, maxFreq));
+}
+extern "C" int sdrgpu_bank_carrier_pll_create(sdrgpu_bank** h, int device, int streams, double bandwidth, double initPhase,
+                                              double initFreq, double minFreq, double maxFreq) {
+    NEED_BANK_OUT(h, "bank_carrier_pll_create");
+    auto* c = new BankPll();
+    return publish_bank(h, c, device, c->configure(streams, PllKind::Carrier, bandwidth, 0, 0, initPhase, initFreq, minFreq, maxFreq));
+}
+extern "C" int sdrgpu_bank_meteor_costas_create(sdrgpu_bank** h, int device, int streams, double bandwidth, int brokenModulation,
+                                                double initPhase, double initFreq, double minFreq, double maxFreq) {
+    NEED_BANK_OUT(h, "bank_meteor_costas_create");
+    auto* c = new BankPll();
+    return publish_bank(h, c, device,
+                        c->configure(streams, PllKind::Meteor, bandwidth, brokenModulation, 0, initPhase, initFreq, minFreq, maxFreq));
+}
+
+// the stages and constants of sdrgpu_meteor_create (symsync.hip)
+extern "C" int sdrgpu_bank_meteor_create(sdrgpu_bank** h, int device, int streams, double symbolrate, double samplerate,
+                                         int rrcTapCount, double rrcBeta, double agcRate, double costasBandwidth,
+                                         int brokenModulation, int oqpsk, double omegaGain, double muGain, double omegaRelLimit) {
+    NEED_BANK_OUT(h, "bank_meteor_create");
+    auto* c = new BankChain();
+    int rc = SDRGPU_OK;
+    if (!Bank::streams_ok(streams)) rc = SDRGPU_EARG;
+    else if (!(symbolrate > 0) || !(samplerate > 0)) { set_error("bank_meteor_create: bad argument"); rc = SDRGPU_EARG; }
+    c->S = std::max(streams, 1);
+    c->in_dtype = c->out_dtype = SDRGPU_C64;
+    if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, configure_rrc(f, streams, SDRGPU_C64, rrcTapCount, rrcBeta, symbolrate, samplerate)); }
+    if (rc >= 0) { auto* a = new BankFastAgc(); rc = c->add(a, a->configure(streams, SDRGPU_C64, 1.0, 10e6, agcRate, 1.0)); }
+    const double PI = 3.1415926535f;   // FL_M_PI, the default frequency limits (meteor_costas.h:13)
+    if (rc >= 0) {
+        auto* l = new BankPll();
+        rc = c->add(l, l->configure(streams, PllKind::Meteor, costasBandwidth, brokenModulation, oqpsk, 0.0, 0.0, -PI, PI));
+    }
     if (rc >= 0) {
         auto* m = new BankMm();
         rc = c->add(m, m->configure(streams, SDRGPU_C64, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8));

@@ -5,12 +5,14 @@
 // frame-major layout: element m of stream k is x[m * S + k] (chan_kernels.h writes out[m * M + k]).
 //   demod::Quadrature, filter::FIR<D, float>      one thread per (row, stream), coalesced over streams
 //   channel::FrequencyXlator                       one block per (row group, 256-stream chunk): the row's phasor is the block's
-//   loop::FastAGC<T>, loop::Costas<ORDER>,
+//   loop::FastAGC<T>, loop::Costas<ORDER>, loop::MeteorCostas,
+//   loop::PLL, loop::CarrierTrackingPLL,
 //   clock_recovery::MM<T>                          one lane per stream
 //
 // The lane-per-stream walk. A workgroup is one wave and owns BANK_W = 64 consecutive streams; lane l
 // is stream k = 64 blockIdx.x + l. Lanes k >= S load and store no stream data and leave at once. The
-// recurrences are the per-sample steps of symsync_kernels.h (fast_agc_step, costas_step, mm_step), so a
+// recurrences are the per-sample steps of symsync_kernels.h (fast_agc_step, costas_step, meteor_costas_step, mm_step;
+// pll_step of loop_steps.h), so a
 // bank column is the single-stream kernel's arithmetic. Per-stream state is structure-of-arrays
 // (word f of stream k at st[f * S + k]): a wave's state load and store are coalesced.
 //
@@ -82,6 +84,54 @@ __global__ __launch_bounds__(BANK_W) void bank_costas_kernel(const float2* __res
         bank_stage(X, in, m0, n, S, k);
         float2* o = out + (size_t)m0 * S + k;
         for (int r = 0; r < n; r++) o[(size_t)r * S] = costas_step<ORDER>(p, X[r * BANK_W + threadIdx.x], phase, freq);
+    }
+    st[k] = phase;
+    st[S + k] = freq;
+}
+
+// ------------------------------------------------------------- MeteorCostas
+// state: phase[S], freq[S]; lastI[S] apart from it (a reset keeps it), read and written only while the
+// stagger is on
+static __global__ __launch_bounds__(BANK_W) void bank_meteor_costas_kernel(const float2* __restrict__ in, float2* __restrict__ out,
+                                                                          int frames, int S, PclParams p, int broken, int oqpsk,
+                                                                          float* __restrict__ st, float* __restrict__ lastIs) {
+    __shared__ float2 X[BANK_F * BANK_W];
+    const int k = blockIdx.x * BANK_W + threadIdx.x;
+    if (k >= S) return;
+    float phase = st[k], freq = st[S + k];
+    float lastI = oqpsk ? lastIs[k] : 0.0f;
+    for (int m0 = 0; m0 < frames; m0 += BANK_F) {
+        const int n = min(BANK_F, frames - m0);
+        bank_stage(X, in, m0, n, S, k);
+        float2* o = out + (size_t)m0 * S + k;
+        for (int r = 0; r < n; r++) {
+            const float2 y = meteor_costas_step(p, broken, X[r * BANK_W + threadIdx.x], phase, freq);
+            o[(size_t)r * S] = oqpsk ? oqpsk_stagger(y, lastI) : y;
+        }
+    }
+    st[k] = phase;
+    st[S + k] = freq;
+    if (oqpsk) lastIs[k] = lastI;
+}
+
+// ------------------------------------------------- PLL, CarrierTrackingPLL
+// state: phase[S], freq[S]
+template <bool DEROTATE>
+__global__ __launch_bounds__(BANK_W) void bank_carrier_pll_kernel(const float2* __restrict__ in, float2* __restrict__ out, int frames,
+                                                                  int S, PllParams p, float* __restrict__ st) {
+    __shared__ float2 X[BANK_F * BANK_W];
+    const int k = blockIdx.x * BANK_W + threadIdx.x;
+    if (k >= S) return;
+    float phase = st[k], freq = st[S + k];
+    for (int m0 = 0; m0 < frames; m0 += BANK_F) {
+        const int n = min(BANK_F, frames - m0);
+        bank_stage(X, in, m0, n, S, k);
+        float2* o = out + (size_t)m0 * S + k;
+        for (int r = 0; r < n; r++) {
+            const float2 v = X[r * BANK_W + threadIdx.x];
+            const float vco = pll_step(p, atan2f(v.y, v.x), phase, freq);
+            o[(size_t)r * S] = pll_output<DEROTATE>(v, vco);
+        }
     }
     st[k] = phase;
     st[S + k] = freq;
@@ -206,29 +256,7 @@ __global__ void bank_quad_kernel(const float2* __restrict__ in, float* __restric
     if (i >= n - S) prevNext[i - (n - S)] = y;
 }
 
-// filter/fir.h:60-80 per stream: out[m S + k] = sum_j buf_k[m + j] taps[j] over [hist (T - 1 rows) || in],
-// ascending taps, fp32, unfused (this translation unit does not contract): the sum does not depend on
-// how the rows are cut into calls. n = frames * S elements, HS = (T - 1) * S history elements. The
-// history carry is carry_history (blocks.h) over the flat stream.
-template <typename DT>
-__global__ void bank_fir_kernel(const DT* __restrict__ in, DT* __restrict__ out, int n, int S, int HS,
-                                const float* __restrict__ taps, int T, const DT* __restrict__ hist) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (the grid's last block may pass INT_MAX)
-    if (i >= n) return;
-    DT acc{};
-    for (int j = 0; j < T; j++) {
-        const long long b = i + (long long)j * S;   // element of [hist || in]
-        const DT x = b < HS ? hist[b] : in[b - HS];
-        const float t = taps[j];
-        if constexpr (sizeof(DT) == 4) {
-            acc += x * t;
-        } else {
-            acc.x += x.x * t;
-            acc.y += x.y * t;
-        }
-    }
-    out[i] = acc;
-}
+// (bank_fir_kernel, filter/fir.h:60-80 per stream, is in symsync_kernels.h: the single-stream Meteor chain runs it too, S = 1)
 
 // ------------------------------------------------------------------- xlator
 // channel/frequency_xlator.h:43-50 per stream, one NCO for the bank: out[m S + k] = in[m S + k] * nco(m),

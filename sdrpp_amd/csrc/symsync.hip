@@ -5,6 +5,10 @@
 //   demod::PSK<ORDER>   demod/psk.h:25-43, 138-143   (RRC FIR -> FastAGC -> Costas -> MM<complex_t>)
 //   demod::GFSK         demod/gfsk.h:24-41, 131-135  (Quadrature -> RRC FIR -> MM<float>)
 //   the RDS chain       decoder_modules/radio/src/demodulators/wfm.h:57-68
+//   loop::PLL, loop::CarrierTrackingPLL   loop/pll.h:15-70, loop/carrier_tracking_pll.h:14-20
+//   loop::MeteorCostas, demod::Meteor     decoder_modules/meteor_demodulator/src/meteor_costas.h:13-56,
+//                       meteor_demod.h:24-43, 139-167 (RRC FIR in the reference's order -> FastAGC -> MeteorCostas with
+//                       the OQPSK stagger -> MM<complex_t>)
 // Top to bottom: the block structs (each: configuration, state, setup / reset, its launch in run), the
 // C entry points. The structs select no device and own no stream: an entry point does, through
 // enter_block or, for a create, itself and publish_block (blocks.h, which also states when an entry
@@ -95,6 +99,88 @@ struct CostasBlock : Block {
         if (order == 2) run_t<2>(in, count, out, s);
         else if (order == 4) run_t<4>(in, count, out, s);
         else run_t<8>(in, count, out, s);
+        p.clampNow = 0;
+        SDRGPU_HIP(hipGetLastError());
+        return count;
+    }
+};
+
+// filter::FIR<complex_t, float> (filter/fir.h:60-80) summed as the reference's VOLK generic kernel sums it: ascending
+// taps, fp32, unfused -- the stream banks' FIR kernel on one stream, the host side of BankFir (bank.hip). demod::Meteor's
+// RRC: with it the chain differs from the reference by the loop's libm alone, and a BankMeteor column is this chain
+// bit for bit. (FirBlock, blocks.hip, picks its kernel and summation order by shape and contracts: it is held to a
+// tolerance, and PSK / GFSK keep it.)
+struct OrderedFirBlock : Block {
+    std::vector<float> taps;
+    DevBuf tapsDev, hist[2];   // hist[cur]: the T - 1 samples before the next call's first
+    int cur = 0;
+    int H() const { return (int)taps.size() - 1; }
+    int setup(int dev, const float* t, int n) {
+        device = dev;
+        in_dtype = out_dtype = SDRGPU_C64;
+        taps.assign(t, t + n);
+        SDRGPU_CHECK(tapsDev.ensure(sizeof(float) * taps.size()));
+        SDRGPU_HIP(hipMemcpy(tapsDev.p, taps.data(), sizeof(float) * taps.size(), hipMemcpyHostToDevice));
+        for (auto& b : hist) SDRGPU_CHECK(b.ensure(sizeof(float2) * (size_t)std::max(H(), 1)));
+        return reset();
+    }
+    int out_count(int count) override { return count; }
+    int reset() override {   // fir.h:49-53
+        SDRGPU_HIP(hipMemset(hist[cur].p, 0, hist[cur].bytes));
+        return SDRGPU_OK;
+    }
+    int run(const void* in, int count, void* out, hipStream_t s) override {
+        if (count < 0) { set_error("fir: negative count"); return SDRGPU_EARG; }
+        if (count == 0) return 0;
+        hipLaunchKernelGGL(bank_fir_kernel<float2>, dim3((count + 255) / 256), dim3(256), 0, s, (const float2*)in, (float2*)out, count,
+                           1, H(), tapsDev.as<float>(), (int)taps.size(), hist[cur].as<float2>());
+        SDRGPU_HIP(hipGetLastError());
+        if (H() > 0) {
+            SDRGPU_CHECK(carry_history(SDRGPU_C64, nullptr, hist[cur], in, hist[cur ^ 1], H(), count, s));
+            cur ^= 1;
+        }
+        return count;
+    }
+};
+
+// loop::MeteorCostas (meteor_costas.h:6-59) is a PLL with its own process, as Costas<ORDER> is: the block is a
+// CostasBlock (coefficients, limits, initial state, reset; the Costas setters reach it) with its own launch.
+struct MeteorCostasBlock : CostasBlock {
+    int broken = 0, oqpsk = 0;
+    DevBuf lastI;   // demod::Meteor's stagger carry (meteor_demod.h:188): 0 at create, no reset touches it
+    int setup(int dev, double bandwidth, int broken_, int oqpsk_, double initPhase_, double initFreq_, double minFreq, double maxFreq) {
+        broken = broken_ ? 1 : 0;
+        oqpsk = oqpsk_ ? 1 : 0;
+        SDRGPU_CHECK(lastI.ensure(sizeof(float)));
+        SDRGPU_HIP(hipMemset(lastI.p, 0, sizeof(float)));
+        return CostasBlock::setup(dev, 4, bandwidth, initPhase_, initFreq_, minFreq, maxFreq);
+    }
+    int run(const void* in, int count, void* out, hipStream_t s) override {
+        if (count < 0) { set_error("meteor_costas: negative count"); return SDRGPU_EARG; }
+        if (count == 0) return 0;
+        const MeteorCostasParams mp{p, broken, oqpsk};
+        hipLaunchKernelGGL(meteor_costas_kernel, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, mp,
+                           state.as<float2>(), lastI.as<float>());
+        p.clampNow = 0;
+        SDRGPU_HIP(hipGetLastError());
+        return count;
+    }
+};
+
+// loop::PLL (pll.h:8-89) and loop::CarrierTrackingPLL (carrier_tracking_pll.h:5-21): a CostasBlock likewise, run by
+// the phase-control-loop step BroadcastFM's pilot PLL runs (pll_step, loop_steps.h)
+struct PllBlock : CostasBlock {
+    bool derotate = false;
+    int run(const void* in, int count, void* out, hipStream_t s) override {
+        if (count < 0) { set_error("pll: negative count"); return SDRGPU_EARG; }
+        if (count == 0) return 0;
+        const PllParams pp = pll_params(p.pcl);
+        if (derotate)
+            hipLaunchKernelGGL(carrier_pll_kernel<true>, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, pp,
+                               p.clampNow, state.as<float2>());
+        else
+            hipLaunchKernelGGL(carrier_pll_kernel<false>, dim3(1), dim3(LOOP_NT), 0, s, (const float2*)in, (float2*)out, count, pp,
+                               p.clampNow, state.as<float2>());
         p.clampNow = 0;
         SDRGPU_HIP(hipGetLastError());
         return count;
@@ -299,6 +385,51 @@ extern "C" int sdrgpu_costas_set_freq_limits(sdrgpu_block* h, double minFreq, do
     return SDRGPU_OK;
 }
 
+// loop::PLL / loop::CarrierTrackingPLL / loop::MeteorCostas: sdrgpu_costas_set_bandwidth and _set_freq_limits are
+// their setBandwidth and setFrequencyLimits too (all four are PLLs, pll.h:27-53)
+static int pll_create(sdrgpu_block** h, int device, bool derotate, double bandwidth, double initPhase, double initFreq,
+                      double minFreq, double maxFreq) {
+    if (!h) { set_error("pll_create: null handle pointer"); return SDRGPU_EARG; }
+    if (!costas_args_ok(4, bandwidth, initPhase, initFreq, minFreq, maxFreq)) return SDRGPU_EARG;   // before the device is touched
+    SDRGPU_SET_DEVICE(device);
+    auto* c = new PllBlock();
+    c->derotate = derotate;
+    return publish_block(h, c, c->setup(device, 4, bandwidth, initPhase, initFreq, minFreq, maxFreq));
+}
+extern "C" int sdrgpu_pll_create(sdrgpu_block** h, int device, double bandwidth, double initPhase, double initFreq, double minFreq,
+                                 double maxFreq) {
+    return pll_create(h, device, false, bandwidth, initPhase, initFreq, minFreq, maxFreq);
+}
+extern "C" int sdrgpu_carrier_pll_create(sdrgpu_block** h, int device, double bandwidth, double initPhase, double initFreq,
+                                         double minFreq, double maxFreq) {
+    return pll_create(h, device, true, bandwidth, initPhase, initFreq, minFreq, maxFreq);
+}
+extern "C" int sdrgpu_meteor_costas_create(sdrgpu_block** h, int device, double bandwidth, int brokenModulation, double initPhase,
+                                           double initFreq, double minFreq, double maxFreq) {
+    if (!h) { set_error("meteor_costas_create: null handle pointer"); return SDRGPU_EARG; }
+    if (!costas_args_ok(4, bandwidth, initPhase, initFreq, minFreq, maxFreq)) return SDRGPU_EARG;   // before the device is touched
+    SDRGPU_SET_DEVICE(device);
+    auto* c = new MeteorCostasBlock();
+    return publish_block(h, c, c->setup(device, bandwidth, brokenModulation, 0, initPhase, initFreq, minFreq, maxFreq));
+}
+// setBrokenModulation (meteor_costas.h:18-22, meteor_demod.h:127-131): from the next call, the loop state is kept
+extern "C" int sdrgpu_meteor_costas_set_broken_modulation(sdrgpu_block* h, int enabled) {
+    auto* c = as_block<MeteorCostasBlock>(h, "a MeteorCostas loop");
+    if (!c) return SDRGPU_EARG;
+    c->broken = enabled ? 1 : 0;
+    return SDRGPU_OK;
+}
+extern "C" int sdrgpu_meteor_set_broken_modulation(sdrgpu_block* h, int enabled) {
+    return sdrgpu_meteor_costas_set_broken_modulation(h, enabled);
+}
+// setOQPSK (meteor_demod.h:133-137): from the next call; lastI keeps the value it had when the stagger last ran
+extern "C" int sdrgpu_meteor_set_oqpsk(sdrgpu_block* h, int enabled) {
+    auto* c = find_kid<MeteorCostasBlock>(h, false);
+    if (!c) { set_error("not a Meteor demodulator"); return SDRGPU_EARG; }
+    c->oqpsk = enabled ? 1 : 0;
+    return SDRGPU_OK;
+}
+
 extern "C" int sdrgpu_mm_create(sdrgpu_block** h, int device, int dtype, double omega, double omegaGain, double muGain,
                                 double omegaRelLimit, int interpPhases, int interpTaps) {
     if (!h || !real_or_complex(dtype)) { set_error("mm_create: bad argument"); return SDRGPU_EARG; }
@@ -367,6 +498,35 @@ extern "C" int sdrgpu_psk_create(sdrgpu_block** h, int device, int order, double
     const double PI = 3.1415926535f;   // FL_M_PI, the default frequency limits (pll.h:15)
     if (rc >= 0) { b = make_costas(device, order, costasBandwidth, 0.0, 0.0, -PI, PI, &rc); rc = append_owned(c, b, rc); }
     if (rc >= 0) {
+        b = make_mm(device, SDRGPU_C64, MmEpilogue::Soft, 1, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8, &rc);
+        rc = append_owned(c, b, rc);
+    }
+    return publish_block(h, c, rc);
+}
+
+// demod::Meteor (meteor_demod.h:24-43, 150-167). Every argument is checked before the device is touched.
+extern "C" int sdrgpu_meteor_create(sdrgpu_block** h, int device, double symbolrate, double samplerate, int rrcTapCount,
+                                    double rrcBeta, double agcRate, double costasBandwidth, int brokenModulation, int oqpsk,
+                                    double omegaGain, double muGain, double omegaRelLimit) {
+    if (!h || !(symbolrate > 0) || !(samplerate > 0)) { set_error("meteor_create: bad argument"); return SDRGPU_EARG; }
+    const double PI = 3.1415926535f;   // FL_M_PI, the default frequency limits (meteor_costas.h:13)
+    std::vector<float> t;
+    SDRGPU_CHECK(design_taps(t, taps_root_raised_cosine, rrcTapCount, rrcBeta, samplerate / symbolrate));
+    if (!costas_args_ok(4, costasBandwidth, 0.0, 0.0, -PI, PI) ||
+        !mm_args_ok(samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8))
+        return SDRGPU_EARG;
+    SDRGPU_SET_DEVICE(device);
+    Block* c = chain_new(device, SDRGPU_C64, SDRGPU_C64);
+    int rc;
+    auto* f = new OrderedFirBlock();   // :31-32
+    Block* b = f;
+    rc = append_owned(c, f, f->setup(device, t.data(), (int)t.size()));
+    if (rc >= 0) { b = make_fast_agc(device, SDRGPU_C64, 1.0, 10e6, agcRate, 1.0, &rc); rc = append_owned(c, b, rc); }   // :33
+    if (rc >= 0) {   // :34, and the stagger of :155-164 on its output
+        auto* m = new MeteorCostasBlock();
+        rc = append_owned(c, m, m->setup(device, costasBandwidth, brokenModulation, oqpsk, 0.0, 0.0, -PI, PI));
+    }
+    if (rc >= 0) {   // :35
         b = make_mm(device, SDRGPU_C64, MmEpilogue::Soft, 1, samplerate / symbolrate, omegaGain, muGain, omegaRelLimit, 128, 8, &rc);
         rc = append_owned(c, b, rc);
     }

@@ -41,6 +41,19 @@ inline bool costas_args_ok(int order, double bandwidth, double initPhase, double
     return true;
 }
 
+// pcl.init(alpha, beta, initPhase, -FL_M_PI, FL_M_PI, initFreq, minFreq, maxFreq) (pll.h:22) as pll_step takes it
+inline PllParams pll_params(const PclParams& pcl) {
+    PllParams pp{};
+    pp.alpha = pcl.alpha;
+    pp.beta = pcl.beta;
+    pp.minPhase = -3.1415926535f;
+    pp.maxPhase = 3.1415926535f;
+    pp.phaseDelta = pp.maxPhase - pp.minPhase;   // phase_control_loop.h:28
+    pp.minFreq = pcl.minFreq;
+    pp.maxFreq = pcl.maxFreq;
+    return pp;
+}
+
 // Every MM output must consume at least one input sample: phase >= 0 before advance, freq >= minFreq and
 // alpha * error >= -alpha, so floorf(phase) >= 1 when minFreq - alpha >= 1 (also in the floats the
 // kernel computes with).

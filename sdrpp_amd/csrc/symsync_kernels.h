@@ -5,6 +5,9 @@
 // Device code of symsync.hip: symbol recovery.
 //   loop::FastAGC<T>                 loop/fast_agc.h:60-79
 //   loop::Costas<ORDER>              loop/costas.h:17-45, loop/phase_control_loop.h:58-85
+//   loop::MeteorCostas               decoder_modules/meteor_demodulator/src/meteor_costas.h:24-56, and the
+//                                    OQPSK stagger of demod::Meteor (meteor_demod.h:155-164)
+//   loop::PLL, CarrierTrackingPLL    loop/pll.h:64-70, loop/carrier_tracking_pll.h:14-20
 //   clock_recovery::MM<T>            clock_recovery/mm.h:100-156
 //   digital::BinarySlicer            digital/binary_slicer.h:12-18
 //   digital::DifferentialDecoder     digital/differential_decoder.h:41-47
@@ -13,10 +16,11 @@
 // call in LOOP_CHUNK-sample chunks staged in LDS, lane 0 runs the recurrence in the reference's
 // operation order, all lanes store the results (serial_chunks.h). State lives on the device between
 // calls and is written back by lane 0. Nothing here uses atomics. The per-sample step of each loop is a
-// __forceinline__ function (fast_agc_step, costas_step, mm_step) that the lane-per-stream kernels of
-// bank_kernels.h call too: a recurrence is stated once.
+// __forceinline__ function (fast_agc_step, costas_step, meteor_costas_step, mm_step; pll_step of
+// loop_steps.h) that the lane-per-stream kernels of bank_kernels.h call too: a recurrence is stated once.
 #pragma once
 #include "serial_chunks.h"
+#include "loop_steps.h"   // PllParams, pll_step
 
 namespace sdrgpu {
 
@@ -83,18 +87,23 @@ __device__ __forceinline__ float costas_error(float re, float im) {   // costas.
     }
     return (err < -1.0f) ? -1.0f : ((1.0f < err) ? 1.0f : err);   // std::clamp<float>
 }
-// one sample (costas.h:17-24, phase_control_loop.h:58-85): the derotated sample out, the loop moved on
-template <int ORDER>
-__device__ __forceinline__ float2 costas_step(const PclParams& p, float2 v, float& phase, float& freq) {
+// one sample of a loop that derotates by its phase (costas.h:17-24, meteor_costas.h:24-30 over
+// phase_control_loop.h:58-85): the derotated sample out, the loop moved on by error(re, im) of that sample
+template <typename Err>
+__device__ __forceinline__ float2 derotate_step(const PclParams& p, float2 v, float& phase, float& freq, Err error) {
     const float PI = 3.1415926535f;                            // FL_M_PI (math/constants.h:4)
     const float minPhase = -PI, maxPhase = PI, phaseDelta = maxPhase - minPhase;
     const float vr = cosf(-phase), vi = sinf(-phase);           // math::phasor(-pcl.phase)
     const float re = (v.x * vr) - (v.y * vi);                   // complex_t::operator* (types.h:23)
     const float im = (v.y * vr) + (v.x * vi);
-    pcl_advance(p, costas_error<ORDER>(re, im), phase, freq);
+    pcl_advance(p, error(re, im), phase, freq);
     while (phase > maxPhase) phase -= phaseDelta;               // clampPhase (:82-85)
     while (phase < minPhase) phase += phaseDelta;
     return make_float2(re, im);
+}
+template <int ORDER>
+__device__ __forceinline__ float2 costas_step(const PclParams& p, float2 v, float& phase, float& freq) {
+    return derotate_step(p, v, phase, freq, [](float re, float im) { return costas_error<ORDER>(re, im); });
 }
 // state: (phase, freq)
 template <int ORDER>
@@ -107,6 +116,101 @@ __global__ __launch_bounds__(LOOP_NT) void costas_kernel(const float2* __restric
         count, [&](int i0, int i) { X[i] = in[i0 + i]; },
         [&](int i) { X[i] = costas_step<ORDER>(p.pcl, X[i], phase, freq); },
         [&](int i0, int i) { out[i0 + i] = X[i]; });
+    if (threadIdx.x == 0) *st = make_float2(phase, freq);
+}
+
+// ------------------------------------------------------------- MeteorCostas
+// math::normalizePhase (math/normalize_phase.h:6-10), the if / else-if as selects of the same values
+// (pll_step, loop_steps.h, says why)
+__device__ __forceinline__ float normalize_phase(float d) {
+    const float PI = 3.1415926535f;
+    return d > PI ? d - 2.0f * PI : (d <= -PI ? d + 2.0f * PI : d);
+}
+// meteor_costas.h:33-56. `broken` is the launch's, not the sample's: the branch is uniform. Without it the
+// error is Costas<4>'s to the letter (:53, :55). With it: the distance of the sample's phase to the
+// nearest of four unevenly spaced constellation phases, scaled by its amplitude.
+__device__ __forceinline__ float meteor_costas_error(float re, float im, int broken) {
+    if (!broken) return costas_error<4>(re, im);
+    const float PHASE1 = (float)0.47439988279190737, PHASE2 = (float)2.1777839908413044;   // :36-39, const float = double
+    const float PHASE3 = (float)3.8682349942715186, PHASE4 = (float)-0.29067248091319986;
+    const float phase = atan2f(im, re);                         // complex_t::phase() (types.h:57-59)
+    const float dp1 = normalize_phase(phase - PHASE1), dp2 = normalize_phase(phase - PHASE2);
+    const float dp3 = normalize_phase(phase - PHASE3), dp4 = normalize_phase(phase - PHASE4);
+    float lowest = dp1;                                         // :46-49, strict comparisons in this order
+    lowest = fabsf(dp2) < fabsf(lowest) ? dp2 : lowest;
+    lowest = fabsf(dp3) < fabsf(lowest) ? dp3 : lowest;
+    lowest = fabsf(dp4) < fabsf(lowest) ? dp4 : lowest;
+    const float err = lowest * amp_of(make_float2(re, im));    // :50, complex_t::amplitude() (types.h:79)
+    return (err < -1.0f) ? -1.0f : ((1.0f < err) ? 1.0f : err);   // std::clamp<float>
+}
+__device__ __forceinline__ float2 meteor_costas_step(const PclParams& p, int broken, float2 v, float& phase, float& freq) {
+    return derotate_step(p, v, phase, freq, [broken](float re, float im) { return meteor_costas_error(re, im, broken); });
+}
+// demod::Meteor's OQPSK stagger of one sample (meteor_demod.h:157-161): the Q arm one sample late
+__device__ __forceinline__ float2 oqpsk_stagger(float2 o, float& lastI) {
+    const float tmp = o.y;
+    o.y = lastI;
+    lastI = tmp;
+    return o;
+}
+struct MeteorCostasParams {
+    CostasParams c;
+    int broken;   // setBrokenModulation (:18-22): a parameter of the call, the loop state is kept
+    int oqpsk;    // demod::Meteor's stagger on the loop's output (off for a MeteorCostas of its own)
+};
+// state: (phase, freq); lastI apart from it (Meteor::reset, meteor_demod.h:139-148, does not touch it), read
+// and written only while the stagger is on. The stagger is data movement on the value lane 0 has in hand.
+static __global__ __launch_bounds__(LOOP_NT) void meteor_costas_kernel(const float2* __restrict__ in, float2* __restrict__ out,
+                                                                       int count, MeteorCostasParams p,
+                                                                       float2* __restrict__ st, float* __restrict__ lastIp) {
+    __shared__ float2 X[LOOP_CHUNK];
+    float phase = st->x, freq = st->y;
+    float lastI = p.oqpsk ? *lastIp : 0.0f;
+    if (p.c.clampNow) pcl_clamp_freq(p.c.pcl, freq);
+    serial_chunks(
+        count, [&](int i0, int i) { X[i] = in[i0 + i]; },
+        [&](int i) {
+            const float2 o = meteor_costas_step(p.c.pcl, p.broken, X[i], phase, freq);
+            X[i] = p.oqpsk ? oqpsk_stagger(o, lastI) : o;
+        },
+        [&](int i0, int i) { out[i0 + i] = X[i]; });
+    if (threadIdx.x == 0) {
+        *st = make_float2(phase, freq);
+        if (p.oqpsk) *lastIp = lastI;
+    }
+}
+
+// ------------------------------------------------- PLL, CarrierTrackingPLL
+// Both run pll_step (loop_steps.h) on the phase of the INPUT sample (pll.h:67, carrier_tracking_pll.h:17) and
+// differ in what they emit for the VCO phase taken before the advance: its phasor (pll.h:66), or the input
+// derotated by it (carrier_tracking_pll.h:16).
+template <bool DEROTATE>
+__device__ __forceinline__ float2 pll_output(float2 v, float vco) {
+    if constexpr (!DEROTATE) {
+        return make_float2(cosf(vco), sinf(vco));               // math::phasor(pcl.phase)
+    } else {
+        const float vr = cosf(-vco), vi = sinf(-vco);           // math::phasor(-pcl.phase)
+        return make_float2((v.x * vr) - (v.y * vi), (v.y * vr) + (v.x * vi));   // complex_t::operator* (types.h:23)
+    }
+}
+// Only pll_step is serial: all lanes take atan2f of the chunk's inputs, lane 0 turns the input phases into
+// VCO phases, all lanes form the outputs. state: (phase, freq)
+template <bool DEROTATE>
+__global__ __launch_bounds__(LOOP_NT) void carrier_pll_kernel(const float2* __restrict__ in, float2* __restrict__ out, int count,
+                                                              PllParams p, int clampNow, float2* __restrict__ st) {
+    __shared__ float2 X[LOOP_CHUNK];
+    __shared__ float T[LOOP_CHUNK];
+    float phase = st->x, freq = st->y;
+    if (clampNow) freq = freq > p.maxFreq ? p.maxFreq : (freq < p.minFreq ? p.minFreq : freq);   // setFreqLimits (:51-56)
+    serial_chunks(
+        count,
+        [&](int i0, int i) {
+            const float2 v = in[i0 + i];
+            X[i] = v;
+            T[i] = atan2f(v.y, v.x);                            // complex_t::phase() (types.h:57-59)
+        },
+        [&](int i) { T[i] = pll_step(p, T[i], phase, freq); },
+        [&](int i0, int i) { out[i0 + i] = pll_output<DEROTATE>(X[i], T[i]); });
     if (threadIdx.x == 0) *st = make_float2(phase, freq);
 }
 
@@ -262,6 +366,35 @@ __global__ __launch_bounds__(LOOP_NT) void mm_kernel(const DT* __restrict__ in, 
         s.outCount = outBase;
         *stp = s;
     }
+}
+
+// ------------------------------------------------- FIR in the reference's order
+// The stream banks' FIR (bank_kernels.h has the layout: element m of stream k at x[m S + k], so the S streams are
+// one flat stream of S-vectors and the sample before element i is element i - S; one thread per element i = m S + k,
+// coalesced over k). demod::Meteor's single-stream chain runs it with S = 1: its RRC then sums exactly as the
+// reference's VOLK generic kernel does, and a BankMeteor column is the single-stream chain bit for bit.
+// filter/fir.h:60-80 per stream: out[m S + k] = sum_j buf_k[m + j] taps[j] over [hist (T - 1 rows) || in],
+// ascending taps, fp32, unfused (this translation unit does not contract): the sum does not depend on
+// how the rows are cut into calls. n = frames * S elements, HS = (T - 1) * S history elements. The
+// history carry is carry_history (blocks.h) over the flat stream.
+template <typename DT>
+__global__ void bank_fir_kernel(const DT* __restrict__ in, DT* __restrict__ out, int n, int S, int HS,
+                                const float* __restrict__ taps, int T, const DT* __restrict__ hist) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // (the grid's last block may pass INT_MAX)
+    if (i >= n) return;
+    DT acc{};
+    for (int j = 0; j < T; j++) {
+        const long long b = i + (long long)j * S;   // element of [hist || in]
+        const DT x = b < HS ? hist[b] : in[b - HS];
+        const float t = taps[j];
+        if constexpr (sizeof(DT) == 4) {
+            acc += x * t;
+        } else {
+            acc.x += x.x * t;
+            acc.y += x.y * t;
+        }
+    }
+    out[i] = acc;
 }
 
 // --------------------------------------------------- slicer, differential decoder

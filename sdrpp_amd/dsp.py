@@ -554,6 +554,50 @@ class Costas(Block):
         check(lib.sdrgpu_costas_set_freq_limits(self._h, float(min_freq), float(max_freq)))
 
 
+_PI32 = float(np.float32(3.1415926535))                        # FL_M_PI, the loops' default frequency limits
+
+
+class _PLLSetters:
+    """setBandwidth / setFrequencyLimits (loop/pll.h:27, 49) of every loop that is a PLL."""
+
+    def set_bandwidth(self, bandwidth):
+        check(lib.sdrgpu_costas_set_bandwidth(self._h, float(bandwidth)))
+
+    def set_freq_limits(self, min_freq, max_freq):
+        check(lib.sdrgpu_costas_set_freq_limits(self._h, float(min_freq), float(max_freq)))
+
+
+class PLL(Block, _PLLSetters):
+    """dsp::loop::PLL (loop/pll.h): the VCO's phasor; arguments in PLL::init's order (loop/pll.h:15)."""
+
+    def __init__(self, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-_PI32, max_freq=_PI32, device=0):
+        h = _make(lib.sdrgpu_pll_create, device, float(bandwidth), float(init_phase), float(init_freq), float(min_freq),
+                  float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class CarrierPLL(Block, _PLLSetters):
+    """dsp::loop::CarrierTrackingPLL (loop/carrier_tracking_pll.h): the input derotated by the VCO; arguments as PLL."""
+
+    def __init__(self, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-_PI32, max_freq=_PI32, device=0):
+        h = _make(lib.sdrgpu_carrier_pll_create, device, float(bandwidth), float(init_phase), float(init_freq), float(min_freq),
+                  float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class MeteorCostas(Block, _PLLSetters):
+    """dsp::loop::MeteorCostas (decoder_modules/meteor_demodulator/src/meteor_costas.h); arguments in its init's order."""
+
+    def __init__(self, bandwidth, broken_modulation=False, init_phase=0.0, init_freq=0.0, min_freq=-_PI32, max_freq=_PI32,
+                 device=0):
+        h = _make(lib.sdrgpu_meteor_costas_create, device, float(bandwidth), int(bool(broken_modulation)), float(init_phase),
+                  float(init_freq), float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+    def set_broken_modulation(self, enabled):
+        check(lib.sdrgpu_meteor_costas_set_broken_modulation(self._h, int(bool(enabled))))
+
+
 class _MMSetters:
     """The MM setters (clock_recovery/mm.h:40-71), on an MM or on a chain that ends in one."""
 
@@ -601,6 +645,27 @@ class PSK(Block, _MMSetters):
         h = _make(lib.sdrgpu_psk_create, device, int(order), float(symbolrate), float(samplerate), int(rrc_taps), float(rrc_beta),
                   float(agc_rate), float(costas_bandwidth), float(omega_gain), float(mu_gain), float(omega_rel_limit))
         super().__init__(h, np.complex64, np.complex64)
+
+
+class Meteor(Block, _MMSetters):
+    """dsp::demod::Meteor (decoder_modules/meteor_demodulator/src/meteor_demod.h), the LRPT demodulator: complex64
+    samples -> complex64 symbols; arguments in its init's order."""
+
+    def __init__(self, symbolrate, samplerate, rrc_taps, rrc_beta, agc_rate, costas_bandwidth, broken_modulation, oqpsk,
+                 omega_gain, mu_gain, omega_rel_limit=0.01, device=0):
+        h = _make(lib.sdrgpu_meteor_create, device, float(symbolrate), float(samplerate), int(rrc_taps), float(rrc_beta),
+                  float(agc_rate), float(costas_bandwidth), int(bool(broken_modulation)), int(bool(oqpsk)), float(omega_gain),
+                  float(mu_gain), float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.complex64)
+
+    def set_broken_modulation(self, enabled):
+        check(lib.sdrgpu_meteor_set_broken_modulation(self._h, int(bool(enabled))))
+
+    def set_oqpsk(self, enabled):
+        check(lib.sdrgpu_meteor_set_oqpsk(self._h, int(bool(enabled))))
+
+    def set_costas_bandwidth(self, bandwidth):
+        check(lib.sdrgpu_costas_set_bandwidth(self._h, float(bandwidth)))
 
 
 class GFSK(Block, _MMSetters):
@@ -747,6 +812,45 @@ class BankPSK(Bank):
         h = _make(lib.sdrgpu_bank_psk_create, device, int(streams), int(order), float(symbolrate), float(samplerate), int(rrc_taps),
                   float(rrc_beta), float(agc_rate), float(costas_bandwidth), float(omega_gain), float(mu_gain),
                   float(omega_rel_limit))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankPLL(Bank):
+    """dsp::loop::PLL per stream; arguments as PLL."""
+
+    def __init__(self, streams, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-_PI32, max_freq=_PI32, device=0):
+        h = _make(lib.sdrgpu_bank_pll_create, device, int(streams), float(bandwidth), float(init_phase), float(init_freq),
+                  float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankCarrierPLL(Bank):
+    """dsp::loop::CarrierTrackingPLL per stream; arguments as CarrierPLL."""
+
+    def __init__(self, streams, bandwidth, init_phase=0.0, init_freq=0.0, min_freq=-_PI32, max_freq=_PI32, device=0):
+        h = _make(lib.sdrgpu_bank_carrier_pll_create, device, int(streams), float(bandwidth), float(init_phase), float(init_freq),
+                  float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankMeteorCostas(Bank):
+    """dsp::loop::MeteorCostas per stream; arguments as MeteorCostas."""
+
+    def __init__(self, streams, bandwidth, broken_modulation=False, init_phase=0.0, init_freq=0.0, min_freq=-_PI32,
+                 max_freq=_PI32, device=0):
+        h = _make(lib.sdrgpu_bank_meteor_costas_create, device, int(streams), float(bandwidth), int(bool(broken_modulation)),
+                  float(init_phase), float(init_freq), float(min_freq), float(max_freq))
+        super().__init__(h, np.complex64, np.complex64)
+
+
+class BankMeteor(Bank):
+    """dsp::demod::Meteor per stream: complex64 samples -> complex64 symbols; arguments as Meteor."""
+
+    def __init__(self, streams, symbolrate, samplerate, rrc_taps, rrc_beta, agc_rate, costas_bandwidth, broken_modulation, oqpsk,
+                 omega_gain, mu_gain, omega_rel_limit=0.01, device=0):
+        h = _make(lib.sdrgpu_bank_meteor_create, device, int(streams), float(symbolrate), float(samplerate), int(rrc_taps),
+                  float(rrc_beta), float(agc_rate), float(costas_bandwidth), int(bool(broken_modulation)), int(bool(oqpsk)),
+                  float(omega_gain), float(mu_gain), float(omega_rel_limit))
         super().__init__(h, np.complex64, np.complex64)
 
 
