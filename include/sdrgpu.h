@@ -169,7 +169,7 @@ int sdrgpu_xlator_create(sdrgpu_block** h, int device, double offsetRad);
 int sdrgpu_xlator_set_offset(sdrgpu_block* h, double offsetRad);
 /* FIR<D,T> (decim = 1) and DecimatingFIR<D,T>: dtype/ttype SDRGPU_F32 or SDRGPU_C64 */
 int sdrgpu_fir_create(sdrgpu_block** h, int device, int dtype, int ttype, const float* taps, int ntaps, int decim);
-int sdrgpu_fir_set_taps(sdrgpu_block* h, const float* taps, int ntaps);
+int sdrgpu_fir_set_taps(sdrgpu_block* h, const float* taps, int ntaps);   /* (also on an AM handle: its low-pass, am.h:51-60) */
 int sdrgpu_fir_set_decimation(sdrgpu_block* h, int decim);
 /* Quadrature (deviation in rad/sample) */
 int sdrgpu_quadrature_create(sdrgpu_block** h, int device, double deviationRad);
@@ -201,7 +201,8 @@ int sdrgpu_agc_get_gain(sdrgpu_block* h, float* gain);         /* agc.h:28 (sync
 /* correction::DCBlocker<T> (correction/dc_blocker.h:17-60); rate = rate_hz / samplerate */
 int sdrgpu_dc_blocker_create(sdrgpu_block** h, int device, int dtype, double rate);
 int sdrgpu_dc_blocker_set_rate(sdrgpu_block* h, double rate);   /* dc_blocker.h:30 (also on an AM handle) */
-/* demod::AM<T> (demod/am.h:27-142): agcMode 0 OFF, 1 CARRIER, 2 AUDIO; stereo != 0 -> stereo_t out */
+/* demod::AM<T> (demod/am.h:27-142): agcMode 0 OFF, 1 CARRIER, 2 AUDIO; stereo != 0 -> stereo_t out.
+ * sdrgpu_block_reset is AM::reset() (am.h:104-112): the AGCs and the DC blocker; the low-pass keeps its history. */
 int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, double bandwidth, double agcAttack, double agcDecay,
                      double dcBlockRate, double samplerate, int stereo);
 /* demod::SSB<T> (demod/ssb.h:20-105): mode 0 USB, 1 LSB, 2 DSB; stereo != 0 -> stereo_t out */
@@ -223,9 +224,13 @@ int sdrgpu_demod_agc_set_attack_decay(sdrgpu_block* h, double attack, double dec
  * pilot band-pass (complex taps) -> PLL (loop/pll.h) -> L+R / L-R matrix -> audio low-pass;
  * stereo_t out. stereo = 0 gives the mono path (= sdrgpu_wfm_create). */
 int sdrgpu_broadcast_fm_create(sdrgpu_block** h, int device, double deviation, double samplerate, int stereo, int lowPass);
-/* RDS branch (broadcast_fm.h:121-127, 164-171, 193-203): setRDSOut; when on, every process call
+/* RDS branch (broadcast_fm.h:121-127, 164-171, 193-203): when on, every process call
  * also produces complex_t RDS baseband = RationalResampler(fs -> 5 kHz)(FrequencyXlator(-57 kHz)(MPX)),
- * read with rds_dev (device pointer + count of the last call) or read_rds (host copy) */
+ * read with rds_dev (device pointer + count of the last call) or read_rds (host copy).
+ * sdrgpu_broadcast_fm_set_rds switches the branch and keeps all state. The reference's setRDSOut also calls
+ * reset(): setRDSOut is sdrgpu_broadcast_fm_set_rds followed by sdrgpu_block_reset.
+ * sdrgpu_block_reset is BroadcastFM::reset() (broadcast_fm.h:130-142): the demodulator, the pilot filter and PLL,
+ * the delays and the audio filters. The RDS branch's xlator phase and resampler history survive it. */
 int sdrgpu_broadcast_fm_set_rds(sdrgpu_block* h, int enabled);
 int sdrgpu_broadcast_fm_rds_dev(sdrgpu_block* h, const void** out, int* n);
 int sdrgpu_broadcast_fm_read_rds(sdrgpu_block* h, void* out, int max);

@@ -89,21 +89,36 @@ def _load():
         "orc_agc_destroy": (None, [vp]),
         "orc_agc_set_gain": (None, [vp, ctypes.c_float]),
         "orc_agc_get_gain": (ctypes.c_float, [vp]),
+        "orc_agc_set_attack_decay": (None, [vp, d, d]),
+        "orc_agc_reset": (None, [vp]),
         "orc_dcb_create": (vp, [i, d]),
         "orc_dcb_process": (i, [vp, vp, i, vp]),
         "orc_dcb_destroy": (None, [vp]),
         "orc_am_create": (vp, [i, d, d, d, d, d, i]),
         "orc_am_process": (i, [vp, vp, i, vp]),
         "orc_am_destroy": (None, [vp]),
+        "orc_am_set_agc_gain": (None, [vp, ctypes.c_float]),
+        "orc_am_set_attack_decay": (None, [vp, d, d]),
+        "orc_am_set_dc_rate": (None, [vp, d]),
+        "orc_am_reset": (None, [vp]),
+        "orc_am_unit_low_pass": (None, [vp]),
         "orc_ssb_create": (vp, [i, d, d, i, d, d]),
         "orc_ssb_process": (i, [vp, vp, i, vp]),
         "orc_ssb_destroy": (None, [vp]),
+        "orc_ssb_set_agc_enabled": (None, [vp, i]),
+        "orc_ssb_set_agc_gain": (None, [vp, ctypes.c_float]),
+        "orc_ssb_set_attack_decay": (None, [vp, d, d]),
+        "orc_cw_create": (vp, [d, i, d, d, d]),
+        "orc_cw_set_tone": (None, [vp, d, d]),
         "orc_compress": (i, [i, vp, i, vp]),
         "orc_decompress": (i, [vp, i, vp]),
         "orc_channelize": (i, [vp, l, vp, i, i, vp, i, vp]),
         "orc_wfms_create": (vp, [d, d, i, i, i]),
         "orc_wfms_process": (i, [vp, vp, i, vp]),
         "orc_wfms_destroy": (None, [vp]),
+        "orc_wfms_reset": (None, [vp]),
+        "orc_wfms_set_rds": (None, [vp, i]),
+        "orc_wfms_rds": (i, [vp, vp]),
         "orc_deemp_create": (vp, [i, d, d]),
         "orc_deemp_process": (i, [vp, vp, i, vp]),
         "orc_deemp_destroy": (None, [vp]),
@@ -412,12 +427,28 @@ class BroadcastFMStereo(_Obj):
     """demod/broadcast_fm.h with the stereo decoder (pilot BPF -> PLL -> L+R / L-R matrix)."""
     _destroy = lib.orc_wfms_destroy
 
-    def __init__(self, deviation, samplerate, stereo=True, low_pass=True, precise=True):
+    def __init__(self, deviation, samplerate, stereo=True, low_pass=True, precise=True, rds=False):
         super().__init__(lib.orc_wfms_create(float(deviation), float(samplerate), int(stereo), int(low_pass), int(precise)),
                          np.complex64, STEREO)
+        if rds:   # init()'s rdsOut argument: the flag alone (every state is still as init() left it)
+            lib.orc_wfms_set_rds(self._h, 1)
 
     def process(self, x):
         return super().process(x, lib.orc_wfms_process)
+
+    def reset(self):
+        """reset() (broadcast_fm.h:130-142): the RDS branch's xlator and resampler keep their state."""
+        lib.orc_wfms_reset(self._h)
+
+    def set_rds(self, enabled):
+        """setRDSOut (broadcast_fm.h:121-128): the flag, then reset()."""
+        lib.orc_wfms_set_rds(self._h, int(bool(enabled)))
+
+    def rds_output(self):
+        """RDS baseband (complex64, 5 kS/s) of the last process() call."""
+        out = np.empty(lib.orc_wfms_rds(self._h, None), np.complex64)
+        lib.orc_wfms_rds(self._h, _p(out))
+        return out
 
 
 class DDCFM(_Obj):
@@ -565,26 +596,75 @@ class DCBlocker(_Obj):
         return super().process(x, lib.orc_dcb_process)
 
 
+def _mono_to_stereo(y):
+    """convert::MonoToStereo"""
+    out = np.empty(len(y), STEREO)
+    out["l"], out["r"] = y, y
+    return out
+
+
 class AM(_Obj):
+    """demod/am.h; ``unit_low_pass``: the low-pass is one unit tap, so process() gives the filter's input."""
     _destroy = lib.orc_am_destroy
 
-    def __init__(self, agc_mode, bandwidth, attack, decay, dc_rate, samplerate, precise=True):
+    def __init__(self, agc_mode, bandwidth, attack, decay, dc_rate, samplerate, precise=True, stereo=False, unit_low_pass=False):
         super().__init__(lib.orc_am_create(int(agc_mode), bandwidth, attack, decay, dc_rate, samplerate, int(precise)),
                          np.complex64, np.float32)
+        self.stereo = stereo
+        if unit_low_pass:
+            lib.orc_am_unit_low_pass(self._h)
 
     def process(self, x):
-        return super().process(x, lib.orc_am_process)
+        y = super().process(x, lib.orc_am_process)
+        return _mono_to_stereo(y) if self.stereo else y
+
+    def set_agc_gain(self, gain):
+        """setAGCGain (am.h:71-75): the audio AGC's gain, in every mode."""
+        lib.orc_am_set_agc_gain(self._h, float(gain))
+
+    def set_agc_attack_decay(self, attack, decay):
+        lib.orc_am_set_attack_decay(self._h, float(attack), float(decay))
+
+    def set_dc_block_rate(self, rate):
+        lib.orc_am_set_dc_rate(self._h, float(rate))
+
+    def reset(self):
+        """reset() (am.h:104-112): both AGCs and the DC blocker; the low-pass keeps its history."""
+        lib.orc_am_reset(self._h)
 
 
 class SSB(_Obj):
     _destroy = lib.orc_ssb_destroy
 
-    def __init__(self, mode, bandwidth, samplerate, agc, attack, decay):
+    def __init__(self, mode, bandwidth, samplerate, agc, attack, decay, stereo=False):
         super().__init__(lib.orc_ssb_create(int(mode), bandwidth, samplerate, int(agc), attack, decay),
                          np.complex64, np.float32)
+        self.stereo = stereo
 
     def process(self, x):
-        return super().process(x, lib.orc_ssb_process)
+        y = super().process(x, lib.orc_ssb_process)
+        return _mono_to_stereo(y) if self.stereo else y
+
+    def set_agc_enabled(self, enabled):
+        lib.orc_ssb_set_agc_enabled(self._h, int(bool(enabled)))
+
+    def set_agc_gain(self, gain):
+        lib.orc_ssb_set_agc_gain(self._h, float(gain))
+
+    def set_agc_attack_decay(self, attack, decay):
+        lib.orc_ssb_set_attack_decay(self._h, float(attack), float(decay))
+
+
+class CW(SSB):
+    """demod/cw.h: SSB's chain with the tone as translation, the AGC's maxOutputAmp and initGain at 1 (cw.h:20)."""
+
+    def __init__(self, tone, agc, attack, decay, samplerate, stereo=False):
+        _Obj.__init__(self, lib.orc_cw_create(float(tone), int(agc), attack, decay, float(samplerate)), np.complex64, np.float32)
+        self.stereo, self.samplerate = stereo, float(samplerate)
+
+    def set_tone(self, tone):
+        """setTone (cw.h:30-35): the phase is kept."""
+        lib.orc_cw_set_tone(self._h, float(tone), self.samplerate)
 
 
 class Chain(_Obj):

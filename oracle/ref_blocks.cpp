@@ -44,6 +44,15 @@
 //   fm  samplerate bandwidth lowPass highPass               demod::FM<float>
 //   ddc  w D                                                FrequencyXlator -> DecimatingFIR<complex_t, float>, block by block
 //   ddcfm  w D dev                                          the same -> Quadrature
+// Analogue demodulators. Ops: `r` reset() (AM, BroadcastFM), `g<x>` setAGCGain(), `e<0|1>` setAGCEnabled() (SSB, CW),
+// `a<att>x<dec>` setAGCAttack() + setAGCDecay(), `b<rate>` AM::setDCBlockRate(), `w<hz>` CW::setTone(), `R<0|1>`
+// BroadcastFM::setRDSOut(). The _s modes write stereo_t. After the outputs the am modes append the low-pass filter's
+// input of every call (float; taken from a twin block given the same calls whose low-pass is one unit tap), the bfm
+// mode the RDS output count of every call (int32) and then every call's RDS samples (complex_t).
+//   am_f|am_s  agcMode bandwidth attack decay dcBlockRate samplerate     demod::AM<float|stereo_t>
+//   ssb_f|ssb_s  mode bandwidth samplerate agcEnabled attack decay       demod::SSB<float|stereo_t>
+//   cw_f|cw_s  tone agcEnabled attack decay samplerate                   demod::CW<float|stereo_t>
+//   bfm  deviation samplerate stereo lowPass rdsOut                      demod::BroadcastFM
 // Design code (no stdin, <calls> ignored; stdout float32 only):
 //   rrc  count beta Ts                                      taps::rootRaisedCosine<float>
 //   mmbank  P T                                             the bank MM builds for itself, [P][T]
@@ -81,14 +90,19 @@
 #include <dsp/multirate/rational_resampler.h>
 #include <dsp/demod/quadrature.h>
 #include <dsp/demod/fm.h>
+#include <dsp/demod/am.h>
+#include <dsp/demod/ssb.h>
+#include <dsp/demod/cw.h>
+#include <dsp/demod/broadcast_fm.h>
 
 using dsp::complex_t;
 using dsp::stereo_t;
 
 struct Op {
-    char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams, 'w' 'f' 'd' 't' 'v' the chain's setters
+    char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams, 'w' 'f' 'd' 't' 'v' the chain's setters,
+                    // 'g' 'e' 'a' 'b' 'R' the demodulators'
     int count = 0, a = 0, b = 0;
-    double v = 0.0;
+    double v = 0.0, v2 = 0.0;
 };
 
 static std::vector<Op> parseCalls(const char* s) {
@@ -106,6 +120,9 @@ static std::vector<Op> parseCalls(const char* s) {
         else if (tok[0] == 'o') { op.kind = 'o'; op.v = strtod(tok.c_str() + 1, NULL); }
         else if (tok[0] == 'i') { op.kind = 'i'; sscanf(tok.c_str() + 1, "%dx%d", &op.a, &op.b); }
         else if (tok[0] == 'w' || tok[0] == 'f' || tok[0] == 'v') { op.kind = tok[0]; op.v = strtod(tok.c_str() + 1, NULL); }
+        else if (tok[0] == 'g' || tok[0] == 'b') { op.kind = tok[0]; op.v = strtod(tok.c_str() + 1, NULL); }
+        else if (tok[0] == 'a') { op.kind = 'a'; sscanf(tok.c_str() + 1, "%lfx%lf", &op.v, &op.v2); }
+        else if (tok[0] == 'e' || tok[0] == 'R') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
         else if (tok[0] == 'd' || tok[0] == 't') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
         else { op.kind = 'p'; op.count = atoi(tok.c_str()); }
         ops.push_back(op);
@@ -122,6 +139,7 @@ static std::vector<T> readInput(size_t n) {
 
 static size_t outPerIn = 1;          // output capacity per input sample (the interpolating resamplers: more than 1)
 static std::vector<uint8_t> tail;    // written after everything else (ddcfm: the FIR-stage outputs)
+static std::vector<uint8_t> tail2;   // written after `tail` (bfm: the RDS samples, after their counts)
 
 // Runs the process() calls of `ops` over stdin; `other` handles the remaining kinds.
 template <class I, class O>
@@ -156,6 +174,7 @@ static int runCalls(const std::vector<Op>& ops, std::function<int(int, I*, O*)> 
     fwrite(y.data(), sizeof(O), op_, stdout);
     if (second) { fwrite(second->data(), 1, second->size(), stdout); }
     fwrite(tail.data(), 1, tail.size(), stdout);
+    fwrite(tail2.data(), 1, tail2.size(), stdout);
     return 0;
 }
 
@@ -390,6 +409,94 @@ static int runDDC(const std::vector<Op>& ops, char** p, bool fm) {
     }, other);
 }
 
+// ------------------------------------------------------------------ analogue demodulators
+template <class V>
+static void append(std::vector<uint8_t>& to, const V* v, size_t n) {
+    const uint8_t* raw = (const uint8_t*)v;
+    to.insert(to.end(), raw, raw + n * sizeof(V));
+}
+
+// AM with its low-pass replaced by one unit tap: its output is the low-pass filter's input
+template <class T>
+struct UnitLowPassAM : dsp::demod::AM<T> {
+    dsp::tap<float> unit;
+    void unitLowPass() {
+        unit = dsp::taps::alloc<float>(1);
+        unit.taps[0] = 1.0f;
+        this->lpf.setTaps(unit);
+    }
+};
+
+template <class T>
+static int runAM(const std::vector<Op>& ops, char** p) {
+    typedef typename dsp::demod::AM<T>::AGCMode Mode;
+    auto& b = zeroed<dsp::demod::AM<T>>();
+    auto& twin = zeroed<UnitLowPassAM<T>>();
+    b.init(NULL, (Mode)atoi(p[0]), atof(p[1]), atof(p[2]), atof(p[3]), atof(p[4]), atof(p[5]));
+    twin.init(NULL, (Mode)atoi(p[0]), atof(p[1]), atof(p[2]), atof(p[3]), atof(p[4]), atof(p[5]));
+    twin.unitLowPass();
+    size_t cap = 1;
+    for (auto& op : ops) { cap = std::max<size_t>(cap, op.count + 1); }
+    std::vector<T> z(cap);
+    return runCalls<complex_t, T>(ops, [&](int n, complex_t* in, T* out) {
+        twin.process(n, in, z.data());
+        for (int i = 0; i < n; i++) { append(tail, (const float*)&z[i], 1); }   // (stereo_t: l, which equals r)
+        return b.process(n, in, out);
+    }, [&](const Op& op) {
+        if (op.kind == 'r') { b.reset(); twin.reset(); }
+        else if (op.kind == 'g') { b.setAGCGain(op.v); twin.setAGCGain(op.v); }
+        else if (op.kind == 'a') { b.setAGCAttack(op.v); b.setAGCDecay(op.v2); twin.setAGCAttack(op.v); twin.setAGCDecay(op.v2); }
+        else if (op.kind == 'b') { b.setDCBlockRate(op.v); twin.setDCBlockRate(op.v); }
+        else { badOp(op); }
+    });
+}
+
+template <class T>
+static int runSSB(const std::vector<Op>& ops, char** p) {
+    typedef typename dsp::demod::SSB<T>::Mode Mode;
+    auto& b = zeroed<dsp::demod::SSB<T>>();
+    b.init(NULL, (Mode)atoi(p[0]), atof(p[1]), atof(p[2]), atoi(p[3]) != 0, atof(p[4]), atof(p[5]));
+    return runCalls<complex_t, T>(ops, [&](int n, complex_t* in, T* out) { return b.process(n, in, out); }, [&](const Op& op) {
+        if (op.kind == 'e') { b.setAGCEnabled(op.a != 0); }
+        else if (op.kind == 'g') { b.setAGCGain(op.v); }
+        else if (op.kind == 'a') { b.setAGCAttack(op.v); b.setAGCDecay(op.v2); }
+        else { badOp(op); }
+    });
+}
+
+template <class T>
+static int runCW(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<dsp::demod::CW<T>>();
+    b.init(NULL, atof(p[0]), atoi(p[1]) != 0, atof(p[2]), atof(p[3]), atof(p[4]));
+    return runCalls<complex_t, T>(ops, [&](int n, complex_t* in, T* out) { return b.process(n, in, out); }, [&](const Op& op) {
+        if (op.kind == 'w') { b.setTone(op.v); }
+        else if (op.kind == 'e') { b.setAGCEnabled(op.a != 0); }
+        else if (op.kind == 'g') { b.setAGCGain(op.v); }
+        else if (op.kind == 'a') { b.setAGCAttack(op.v); b.setAGCDecay(op.v2); }
+        else { badOp(op); }
+    });
+}
+
+static int runBFM(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<dsp::demod::BroadcastFM>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atoi(p[2]) != 0, atoi(p[3]) != 0, atoi(p[4]) != 0);
+    size_t cap = 1;
+    for (auto& op : ops) { cap = std::max<size_t>(cap, op.count + 1); }
+    std::vector<complex_t> rds(cap);
+    return runCalls<complex_t, stereo_t>(ops, [&](int n, complex_t* in, stereo_t* out) {
+        int nrds = 0;
+        int m = b.process(n, in, out, nrds, rds.data());
+        int32_t c = nrds;
+        append(tail, &c, 1);
+        append(tail2, rds.data(), nrds);
+        return m;
+    }, [&](const Op& op) {
+        if (op.kind == 'r') { b.reset(); }
+        else if (op.kind == 'R') { b.setRDSOut(op.a != 0); }
+        else { badOp(op); }
+    });
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { return 2; }
     std::string mode = argv[1];
@@ -488,6 +595,14 @@ int main(int argc, char** argv) {
     }
     if (mode == "ddc" && np == 2) { return runDDC(ops, p, false); }
     if (mode == "ddcfm" && np == 3) { return runDDC(ops, p, true); }
+
+    if (mode == "am_f" && np == 6) { return runAM<float>(ops, p); }
+    if (mode == "am_s" && np == 6) { return runAM<stereo_t>(ops, p); }
+    if (mode == "ssb_f" && np == 6) { return runSSB<float>(ops, p); }
+    if (mode == "ssb_s" && np == 6) { return runSSB<stereo_t>(ops, p); }
+    if (mode == "cw_f" && np == 5) { return runCW<float>(ops, p); }
+    if (mode == "cw_s" && np == 5) { return runCW<stereo_t>(ops, p); }
+    if (mode == "bfm" && np == 5) { return runBFM(ops, p); }
 
     if (mode == "rrc" && np == 3) {
         dsp::tap<float> t = dsp::taps::rootRaisedCosine<float>(atoi(p[0]), atof(p[1]), atof(p[2]));

@@ -112,6 +112,39 @@ void volk_32fc_deinterleave_real_32f(float* iBuffer, const lv_32fc_t* complexVec
     for (unsigned int i = 0; i < num_points; i++) { iBuffer[i] = in[2 * i]; }
 }
 
+// The elementwise kernels of the analogue demodulators (demod/broadcast_fm.h, convert/*.h, math/*.h): one plain loop
+// each, one rounding per operation; none of them sums.
+void volk_32f_s32f_multiply_32f(float* cVector, const float* aVector, const float scalar, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { cVector[i] = aVector[i] * scalar; }
+}
+
+void volk_32fc_conjugate_32fc(lv_32fc_t* cVector, const lv_32fc_t* aVector, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { cVector[i] = lv_cmake(aVector[i].real(), -aVector[i].imag()); }
+}
+
+void volk_32fc_x2_multiply_32fc(lv_32fc_t* cVector, const lv_32fc_t* aVector, const lv_32fc_t* bVector, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) {
+        const float ar = aVector[i].real(), ai = aVector[i].imag(), br = bVector[i].real(), bi = bVector[i].imag();
+        cVector[i] = lv_cmake((ar * br) - (ai * bi), (ar * bi) + (ai * br));
+    }
+}
+
+void volk_32f_x2_multiply_32f(float* cVector, const float* aVector, const float* bVector, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { cVector[i] = aVector[i] * bVector[i]; }
+}
+
+void volk_32f_x2_add_32f(float* cVector, const float* aVector, const float* bVector, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { cVector[i] = aVector[i] + bVector[i]; }
+}
+
+void volk_32f_x2_subtract_32f(float* cVector, const float* aVector, const float* bVector, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { cVector[i] = aVector[i] - bVector[i]; }
+}
+
+void volk_32f_x2_interleave_32fc(lv_32fc_t* complexVector, const float* iBuffer, const float* qBuffer, unsigned int num_points) {
+    for (unsigned int i = 0; i < num_points; i++) { complexVector[i] = lv_cmake(iBuffer[i], qBuffer[i]); }
+}
+
 // VOLK's generic rotator as published (volk_32fc_s32fc_x2_rotator_32fc_generic): out = in * phase, phase
 // *= phase_inc in fp32, phase renormalised after every 512 samples and once more at the end of a call
 // that leaves a remainder. With -DREF_ROT64 the phase is carried in fp64 beside the block's fp32 copy

@@ -757,6 +757,8 @@ struct orc_wfms {
     orc_quad* q; orc_fir *pilot, *al, *ar; struct orc_pll pll;
     int stereo, lowPass, delay;
     float *mpx, *cplx, *pf, *vco, *lmr, *l, *r, *dlpr, *dlmr; int cap;
+    /* the RDS branch (broadcast_fm.h:52-53, 164-171, 193-203): MPX as complex -> xlator(-57 kHz) -> resampler(fs -> 5 kHz) */
+    int rdsOn, rdsCount; orc_xlator* rdsX; orc_rres* rdsR; float *rdsIn, *rdsOut;
 };
 orc_wfms* orc_wfms_create(double deviation, double samplerate, int stereo, int lowPass, int precise) {
     orc_wfms* w = (orc_wfms*)calloc(1, sizeof(orc_wfms));
@@ -778,7 +780,30 @@ orc_wfms* orc_wfms_create(double deviation, double samplerate, int stereo, int l
     w->stereo = stereo; w->lowPass = lowPass;
     w->dlpr = (float*)calloc(w->delay, sizeof(float));            /* Delay<float> state */
     w->dlmr = (float*)calloc(2 * w->delay, sizeof(float));        /* Delay<complex_t> state */
+    w->rdsX = orc_xlator_create(hz_to_rads(-57000.0, samplerate));
+    w->rdsR = orc_rres_create(ORC_C64, samplerate, 5000.0, precise);
     return w;
+}
+/* reset() (broadcast_fm.h:130-142): demod, pilotFir, pilotPLL, both delays, both audio FIRs. The RDS branch's xlator
+ * and resampler are not reset: the NCO phase and the resampler's history survive. */
+void orc_wfms_reset(orc_wfms* w) {
+    orc_quad_reset(w->q);
+    orc_fir_reset(w->pilot);
+    w->pll.phase = w->pll.initPhase; w->pll.freq = w->pll.initFreq;      /* phase_control_loop.h reset() */
+    memset(w->dlpr, 0, sizeof(float) * w->delay);
+    memset(w->dlmr, 0, sizeof(float) * 2 * w->delay);
+    orc_fir_reset(w->al);
+    orc_fir_reset(w->ar);
+}
+void orc_wfms_set_rds(orc_wfms* w, int on) { w->rdsOn = on; orc_wfms_reset(w); }   /* setRDSOut (:121-128): reset() */
+/* the RDS samples of the last process call */
+int orc_wfms_rds(orc_wfms* w, float* out) {
+    if (out) memcpy(out, w->rdsOut, sizeof(float) * 2 * w->rdsCount);
+    return w->rdsCount;
+}
+static void orc_wfms_rds_branch(orc_wfms* w, const float* cplx, int count) {
+    orc_xlator_process(w->rdsX, cplx, count, w->rdsIn);
+    w->rdsCount = orc_rres_process(w->rdsR, w->rdsIn, count, w->rdsOut);
 }
 static void orc_delay(float* state, int delay, int e, const float* in, int count, float* out) {
     /* math/delay.h:39-50: out = [state || in][0:count], state = last `delay` of [state || in] */
@@ -796,10 +821,17 @@ int orc_wfms_process(orc_wfms* w, const float* in, int count, float* out) {
         w->pf = (float*)malloc(sizeof(float) * 2 * count); w->vco = (float*)malloc(sizeof(float) * 2 * count);
         w->lmr = (float*)malloc(sizeof(float) * 2 * count); w->l = (float*)malloc(sizeof(float) * count);
         w->r = (float*)malloc(sizeof(float) * count);
+        free(w->rdsIn); free(w->rdsOut);
+        w->rdsIn = (float*)malloc(sizeof(float) * 2 * (count + 1)); w->rdsOut = (float*)malloc(sizeof(float) * 2 * (count + 64));
         w->cap = count;
     }
+    w->rdsCount = 0;
     orc_quad_process(w->q, in, count, w->mpx);
     if (!w->stereo) {
+        if (w->rdsOn) {
+            for (int i = 0; i < count; i++) { w->cplx[2 * i] = w->mpx[i]; w->cplx[2 * i + 1] = 0.0f; }   /* RealToComplex */
+            orc_wfms_rds_branch(w, w->cplx, count);
+        }
         if (w->lowPass) orc_fir_process(w->al, w->mpx, count, w->mpx);
         for (int i = 0; i < count; i++) { out[2 * i] = w->mpx[i]; out[2 * i + 1] = w->mpx[i]; }
         return count;
@@ -809,6 +841,7 @@ int orc_wfms_process(orc_wfms* w, const float* in, int count, float* out) {
     orc_pll_process(&w->pll, w->pf, count, w->vco);
     orc_delay(w->dlpr, w->delay, 1, w->mpx, count, w->mpx);          /* lprDelay (in place) */
     orc_delay(w->dlmr, w->delay, 2, w->cplx, count, w->lmr);         /* lmrDelay */
+    if (w->rdsOn) orc_wfms_rds_branch(w, w->cplx, count);            /* (the undelayed MPX; :164-171) */
     for (int i = 0; i < count; i++) {
         float vr = w->vco[2 * i], vi = -w->vco[2 * i + 1];            /* Conjugate */
         for (int k = 0; k < 2; k++) {                                  /* Multiply<complex_t> twice */
@@ -831,6 +864,7 @@ void orc_wfms_destroy(orc_wfms* w) {
     if (!w) return;
     orc_quad_destroy(w->q); orc_fir_destroy(w->pilot); orc_fir_destroy(w->al); orc_fir_destroy(w->ar);
     free(w->mpx); free(w->cplx); free(w->pf); free(w->vco); free(w->lmr); free(w->l); free(w->r);
+    orc_xlator_destroy(w->rdsX); orc_rres_destroy(w->rdsR); free(w->rdsIn); free(w->rdsOut);
     free(w->dlpr); free(w->dlmr); free(w);
 }
 
@@ -886,6 +920,14 @@ orc_agc* orc_agc_create(int dtype, double setPoint, double attack, double decay,
 void orc_agc_set_enabled(orc_agc* a, int en) { a->enabled = en; }
 void orc_agc_set_gain(orc_agc* a, float g) { a->gain = g; }   /* agc.h:31-35 */
 float orc_agc_get_gain(orc_agc* a) { return a->gain; }
+void orc_agc_set_attack_decay(orc_agc* a, double attack, double decay) {   /* agc.h:49-61 */
+    a->attack = (float)attack; a->invAttack = 1.0f - a->attack;
+    a->decay = (float)decay; a->invDecay = 1.0f - a->decay;
+}
+void orc_agc_reset(orc_agc* a) {                                            /* agc.h:81-86 */
+    a->amp = a->setPoint / a->initGain;
+    a->gain = a->initGain < a->maxGain ? a->initGain : a->maxGain;
+}
 static float amp_of(const float* x, int dtype, int i) {
     if (dtype == ORC_C64) { float re = x[2 * i], im = x[2 * i + 1]; return sqrtf((re * re) + (im * im)); }
     return fabsf(x[i]);
@@ -938,6 +980,8 @@ int orc_dcb_process(orc_dcb* d, const float* in, int count, float* out) {
         }
     return count;
 }
+void orc_dcb_set_rate(orc_dcb* d, double rate) { d->rate = (float)rate; }   /* dc_blocker.h:30-34 */
+void orc_dcb_reset(orc_dcb* d) { d->off[0] = 0.0f; d->off[1] = 0.0f; }       /* dc_blocker.h:36-46 */
 void orc_dcb_destroy(orc_dcb* d) { free(d); }
 
 /* ------------------------------------------------------------------- AM */
@@ -971,6 +1015,17 @@ int orc_am_process(orc_am* a, const float* in, int count, float* out) {
     orc_fir_process(a->lpf, out, count, out);
     return count;
 }
+/* am.h:71-112: setAGCGain reaches the audio AGC only, attack and decay both AGCs; reset() resets the two AGCs and
+ * the DC blocker and leaves the low-pass filter's history */
+void orc_am_set_agc_gain(orc_am* a, float gain) { orc_agc_set_gain(a->audio, gain); }
+void orc_am_set_attack_decay(orc_am* a, double attack, double decay) {
+    orc_agc_set_attack_decay(a->carrier, attack, decay);
+    orc_agc_set_attack_decay(a->audio, attack, decay);
+}
+void orc_am_set_dc_rate(orc_am* a, double rate) { orc_dcb_set_rate(a->dcb, rate); }
+void orc_am_reset(orc_am* a) { orc_agc_reset(a->carrier); orc_agc_reset(a->audio); orc_dcb_reset(a->dcb); }
+/* test access: the low-pass replaced by one unit tap, so that process() gives the filter's input */
+void orc_am_unit_low_pass(orc_am* a) { float one = 1.0f; orc_fir_set_taps(a->lpf, &one, 1); }
 void orc_am_destroy(orc_am* a) {
     if (!a) return;
     orc_agc_destroy(a->carrier); orc_agc_destroy(a->audio); orc_dcb_destroy(a->dcb); orc_fir_destroy(a->lpf); free(a->tmp); free(a);
@@ -994,6 +1049,19 @@ int orc_ssb_process(orc_ssb* s, const float* in, int count, float* out) {
     orc_agc_process(s->agc, out, count, out);
     return count;
 }
+void orc_ssb_set_agc_enabled(orc_ssb* s, int en) { orc_agc_set_enabled(s->agc, en); }   /* ssb.h:64-88, cw.h:37-63 */
+void orc_ssb_set_agc_gain(orc_ssb* s, float gain) { orc_agc_set_gain(s->agc, gain); }
+void orc_ssb_set_attack_decay(orc_ssb* s, double attack, double decay) { orc_agc_set_attack_decay(s->agc, attack, decay); }
+/* demod/cw.h:15-35, 72-85 (T = float): SSB's chain with the tone as the translation and the AGC's maxOutputAmp and
+ * initGain at 1 (cw.h:20); setTone keeps the xlator's phase */
+orc_ssb* orc_cw_create(double tone, int agcEnabled, double agcAttack, double agcDecay, double samplerate) {
+    orc_ssb* s = (orc_ssb*)calloc(1, sizeof(orc_ssb));
+    s->x = orc_xlator_create(hz_to_rads(tone, samplerate));
+    s->agc = orc_agc_create(ORC_F32, 1.0, agcAttack, agcDecay, 10e6, 1.0, 1.0);
+    orc_agc_set_enabled(s->agc, agcEnabled);
+    return s;
+}
+void orc_cw_set_tone(orc_ssb* s, double tone, double samplerate) { orc_xlator_set_offset(s->x, hz_to_rads(tone, samplerate)); }
 void orc_ssb_destroy(orc_ssb* s) { if (!s) return; orc_xlator_destroy(s->x); orc_agc_destroy(s->agc); free(s->tmp); free(s); }
 
 /* ----------------------------------------------------------- compression */

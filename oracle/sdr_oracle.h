@@ -123,6 +123,9 @@ typedef struct orc_wfms orc_wfms;            /* demod/broadcast_fm.h, stereo or 
 orc_wfms* orc_wfms_create(double deviation, double samplerate, int stereo, int lowPass, int precise);
 int  orc_wfms_process(orc_wfms* w, const float* in, int count, float* out_stereo);
 void orc_wfms_destroy(orc_wfms* w);
+void orc_wfms_reset(orc_wfms* w);            /* reset(): the RDS branch keeps its state */
+void orc_wfms_set_rds(orc_wfms* w, int on);  /* setRDSOut: the flag, then reset() */
+int  orc_wfms_rds(orc_wfms* w, float* out);  /* the RDS samples (complex) of the last process call */
 
 typedef struct orc_fm orc_fm;                /* demod/fm.h */
 orc_fm* orc_fm_create(double samplerate, double bandwidth, int lowPass, int highPass, int precise);
@@ -136,23 +139,37 @@ orc_agc* orc_agc_create(int dtype, double setPoint, double attack, double decay,
 void orc_agc_set_enabled(orc_agc* a, int en);
 void orc_agc_set_gain(orc_agc* a, float g);
 float orc_agc_get_gain(orc_agc* a);
+void orc_agc_set_attack_decay(orc_agc* a, double attack, double decay);
+void orc_agc_reset(orc_agc* a);
 int  orc_agc_process(orc_agc* a, const float* in, int count, float* out);
 void orc_agc_destroy(orc_agc* a);
 
 typedef struct orc_dcb orc_dcb;              /* correction/dc_blocker.h */
 orc_dcb* orc_dcb_create(int dtype, double rate);
 int  orc_dcb_process(orc_dcb* d, const float* in, int count, float* out);
+void orc_dcb_set_rate(orc_dcb* d, double rate);
+void orc_dcb_reset(orc_dcb* d);
 void orc_dcb_destroy(orc_dcb* d);
 
 typedef struct orc_am orc_am;                /* demod/am.h (float output) */
 orc_am* orc_am_create(int agcMode, double bandwidth, double agcAttack, double agcDecay, double dcBlockRate, double samplerate, int precise);
 int  orc_am_process(orc_am* a, const float* in, int count, float* out);
 void orc_am_destroy(orc_am* a);
+void orc_am_set_agc_gain(orc_am* a, float gain);
+void orc_am_set_attack_decay(orc_am* a, double attack, double decay);
+void orc_am_set_dc_rate(orc_am* a, double rate);
+void orc_am_reset(orc_am* a);                /* both AGCs and the DC blocker, not the low-pass */
+void orc_am_unit_low_pass(orc_am* a);        /* test access: process() gives the low-pass filter's input */
 
 typedef struct orc_ssb orc_ssb;              /* demod/ssb.h (float output) */
 orc_ssb* orc_ssb_create(int mode, double bandwidth, double samplerate, int agcEnabled, double agcAttack, double agcDecay);
 int  orc_ssb_process(orc_ssb* s, const float* in, int count, float* out);
 void orc_ssb_destroy(orc_ssb* s);
+void orc_ssb_set_agc_enabled(orc_ssb* s, int en);
+void orc_ssb_set_agc_gain(orc_ssb* s, float gain);
+void orc_ssb_set_attack_decay(orc_ssb* s, double attack, double decay);
+orc_ssb* orc_cw_create(double tone, int agcEnabled, double agcAttack, double agcDecay, double samplerate);   /* demod/cw.h */
+void orc_cw_set_tone(orc_ssb* s, double tone, double samplerate);
 
 /* compression (dsp/compression/sample_stream_{compressor,decompressor}.h) */
 int orc_compress(int pcmType, const float* in, int count, uint8_t* out);

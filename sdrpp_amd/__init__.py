@@ -143,6 +143,8 @@ def _load():
         "sdrgpu_demod_agc_set_gain": (i, [vp, i, ctypes.c_float]),
         "sdrgpu_demod_agc_get_gain": (i, [vp, i, ctypes.POINTER(ctypes.c_float)]),
         "sdrgpu_demod_agc_set_enabled": (i, [vp, i, i]),
+        "sdrgpu_demod_agc_set_attack_decay": (i, [vp, d, d]),
+        "sdrgpu_dc_blocker_set_rate": (i, [vp, d]),
         "sdrgpu_fmif_create": (i, [pp, i, i]),
         "sdrgpu_fmif_set_bins": (i, [vp, i]),
         "sdrgpu_fmif_window": (i, [i, fp]),

@@ -834,6 +834,7 @@ struct BankMonoPairs : Bank {
 struct BankChain : Bank {
     std::vector<std::unique_ptr<Bank>> kids;
     DevBuf buf[2];
+    size_t keepOnReset = 0;   // the last stages that reset() leaves as they are (AM's low-pass, am.h:104-112)
     // a configured stage joins (rc: its configure's status)
     int add(Bank* b, int rc) {
         std::unique_ptr<Bank> k(b);
@@ -849,7 +850,7 @@ struct BankChain : Bank {
         return SDRGPU_OK;
     }
     int reset() override {
-        for (auto& k : kids) SDRGPU_CHECK(k->reset());
+        for (size_t i = 0; i + keepOnReset < kids.size(); i++) SDRGPU_CHECK(kids[i]->reset());
         return SDRGPU_OK;
     }
     bool ragged() const override { return kids.back()->ragged(); }
@@ -1140,6 +1141,7 @@ extern "C" int sdrgpu_bank_am_create(sdrgpu_bank** h, int device, int streams, i
         std::vector<float> t;
         rc = design_taps(t, taps_low_pass, fc, fc * 0.1, samplerate, 0);
         if (rc >= 0) { auto* f = new BankFir(); rc = c->add(f, f->configure(streams, SDRGPU_F32, t.data(), (int)t.size())); }
+        if (rc >= 0) c->keepOnReset = 1;   // reset() (am.h:104-112): the AGCs and the DC blocker, not lpf
     }
     return publish_bank(h, c, device, rc);
 }

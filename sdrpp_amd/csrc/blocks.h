@@ -15,6 +15,8 @@ inline int append_owned(Block* chain, Block* b, int rc) {
     if (rc < 0) { delete b; return rc; }
     return chain_append(chain, b);
 }
+// the chain's reset() leaves its last `lastKids` kids as they are
+int chain_keep_on_reset(Block* chain, int lastKids);
 int chain_size(Block* chain);
 Block* chain_kid(Block* chain, int i);
 // the first (or last) kid of type T of the chain behind h; null where h is no chain or has none

@@ -666,12 +666,13 @@ struct PolyBlock : Block {
 struct ChainBlock : Block {
     std::vector<std::unique_ptr<Block>> kids;
     DevBuf scratch[2];
+    size_t keepOnReset = 0;   // the last kids that reset() leaves as they are (AM's low-pass, am.h:104-112)
     int out_count(int count) override {
         for (auto& k : kids) count = k->out_count(count);   // (does not mutate state)
         return count;
     }
     int reset() override {
-        for (auto& k : kids) SDRGPU_CHECK(k->reset());
+        for (size_t i = 0; i + keepOnReset < kids.size(); i++) SDRGPU_CHECK(kids[i]->reset());
         return SDRGPU_OK;
     }
     int run(const void* in, int count, void* out, hipStream_t s) override {
@@ -861,6 +862,12 @@ int chain_append(Block* chain, Block* kid) {
     auto* c = dynamic_cast<ChainBlock*>(chain);
     if (!c || !kid) { delete kid; set_error("chain_append: bad argument"); return SDRGPU_EARG; }
     c->kids.emplace_back(kid);
+    return SDRGPU_OK;
+}
+int chain_keep_on_reset(Block* chain, int lastKids) {
+    auto* c = dynamic_cast<ChainBlock*>(chain);
+    if (!c || lastKids < 0 || (size_t)lastKids > c->kids.size()) { set_error("chain_keep_on_reset: bad argument"); return SDRGPU_EARG; }
+    c->keepOnReset = (size_t)lastKids;
     return SDRGPU_OK;
 }
 int chain_size(Block* chain) {
@@ -1111,6 +1118,7 @@ extern "C" int sdrgpu_fir_create(sdrgpu_block** h, int device, int dtype, int tt
 extern "C" int sdrgpu_fir_set_taps(sdrgpu_block* h, const float* taps, int ntaps) {
     SDRGPU_CHECK(enter_block(h, true));
     auto* f = dynamic_cast<FirBlock*>(h->impl);
+    if (!f) f = find_kid<FirBlock>(h, true);   // the AM chain's low-pass (am.h:51-60)
     if (!f) { set_error("not a FIR"); return SDRGPU_ESTATE; }
     return f->set_taps(taps, ntaps);
 }

@@ -272,11 +272,10 @@ struct BroadcastFmBlock : Block {
         return reset();
     }
     int out_count(int count) override { return count; }
-    int reset() override {   // broadcast_fm.h:129-141
+    int reset() override {   // broadcast_fm.h:130-142: not the RDS branch, whose NCO phase and resampler history survive
         SDRGPU_CHECK(quad->reset());
         SDRGPU_CHECK(pilot->reset());
         SDRGPU_CHECK(audio->reset());
-        if (rdsChain) SDRGPU_CHECK(rdsChain->reset());
         const float2 st = make_float2(initPhase, initFreq);
         SDRGPU_HIP(hipMemcpy(pllState.p, &st, sizeof(st), hipMemcpyHostToDevice));
         SDRGPU_HIP(hipMemset(hist[cur].p, 0, sizeof(float) * delay));
@@ -488,6 +487,7 @@ extern "C" int sdrgpu_am_create(sdrgpu_block** h, int device, int agcMode, doubl
         if (rc >= 0) {
             Block* f = make_fir_block(device, SDRGPU_F32, SDRGPU_F32, t.data(), (int)t.size(), 1, stereo != 0, &rc);
             rc = append_owned(c, f, rc);
+            if (rc >= 0) rc = chain_keep_on_reset(c, 1);   // reset() (am.h:104-112): the AGCs and the DC blocker, not lpf
         }
     }
     return publish_block(h, c, rc);

@@ -220,6 +220,11 @@ class BroadcastFM(Block):
         """setRDSOut (broadcast_fm.h:121-127)."""
         check(lib.sdrgpu_broadcast_fm_set_rds(self._h, int(bool(enabled))))
 
+    def set_rds_out(self, enabled):
+        """The reference's setRDSOut (broadcast_fm.h:121-128): the flag, then reset()."""
+        self.set_rds(enabled)
+        self.reset()
+
     def rds_output(self):
         """RDS baseband (complex64, 5 kS/s) produced by the last process() call."""
         n = ctypes.c_int()
@@ -1064,9 +1069,39 @@ class AM(Block):
         h = _make(lib.sdrgpu_am_create, device, int(agc_mode), float(bandwidth), float(attack), float(decay),
                   float(dc_rate), float(samplerate), int(bool(stereo)))
         super().__init__(h, np.complex64, STEREO if stereo else np.float32)
+        self._carrier = int(agc_mode) == 1
+
+    def set_agc_gain(self, gain):
+        """setAGCGain (am.h:71-75): the audio AGC, which CARRIER mode does not run."""
+        if not self._carrier:
+            check(lib.sdrgpu_demod_agc_set_gain(self._h, 1, float(gain)))
+
+    def set_agc_attack_decay(self, attack, decay):
+        check(lib.sdrgpu_demod_agc_set_attack_decay(self._h, float(attack), float(decay)))
+
+    def set_dc_block_rate(self, rate):
+        check(lib.sdrgpu_dc_blocker_set_rate(self._h, float(rate)))
+
+    def set_low_pass_taps(self, taps):
+        """The low-pass filter's taps (what setBandwidth designs anew, am.h:51-60); the history is kept."""
+        t = np.ascontiguousarray(taps, np.float32)
+        check(lib.sdrgpu_fir_set_taps(self._h, _fptr(t), int(t.shape[0])))
 
 
-class SSB(Block):
+class _DemodAgcSetters:
+    """setAGCEnabled / setAGCGain / setAGCAttack + setAGCDecay of SSB and CW (ssb.h:64-88, cw.h:37-63)."""
+
+    def set_agc_enabled(self, enabled):
+        check(lib.sdrgpu_demod_agc_set_enabled(self._h, 0, int(bool(enabled))))
+
+    def set_agc_gain(self, gain):
+        check(lib.sdrgpu_demod_agc_set_gain(self._h, 0, float(gain)))
+
+    def set_agc_attack_decay(self, attack, decay):
+        check(lib.sdrgpu_demod_agc_set_attack_decay(self._h, float(attack), float(decay)))
+
+
+class SSB(Block, _DemodAgcSetters):
     """dsp::demod::SSB<T> (demod/ssb.h); mode 0 USB, 1 LSB, 2 DSB."""
 
     def __init__(self, mode, bandwidth, samplerate, agc_enabled, attack, decay, stereo=False, device=0):
@@ -1075,7 +1110,7 @@ class SSB(Block):
         super().__init__(h, np.complex64, STEREO if stereo else np.float32)
 
 
-class CW(Block):
+class CW(Block, _DemodAgcSetters):
     """dsp::demod::CW<T> (demod/cw.h); arguments in CW::init's order."""
 
     def __init__(self, tone, agc_enabled, attack, decay, samplerate, stereo=False, device=0):

@@ -76,7 +76,17 @@ public:
     void setSamplerate(double samplerate) { set(samplerate, _stereo, _lowPass, _rdsOut); }
     void setStereo(bool stereo) { set(_samplerate, stereo, _lowPass, _rdsOut); }
     void setLowPass(bool lowPass) { set(_samplerate, _stereo, lowPass, _rdsOut); }
-    void setRDSOut(bool rdsOut) { set(_samplerate, _stereo, _lowPass, rdsOut); }
+    // setRDSOut (:121-128) is the flag and reset(): the RDS branch's xlator phase and resampler history survive, so a
+    // handle that has the branch is kept (sdrgpu_broadcast_fm_set_rds, then sdrgpu_block_reset). The mono handle has
+    // no RDS branch and none has run yet: a new handle loses nothing that reset() would have kept.
+    void setRDSOut(bool rdsOut) {
+        if (!_full) { set(_samplerate, _stereo, _lowPass, rdsOut); return; }
+        std::lock_guard<std::recursive_mutex> lck(base_type::ctrlMtx);
+        base_type::tempStop();
+        _rdsOut = rdsOut;
+        if (gpu::ok(sdrgpu_broadcast_fm_set_rds(_h.h, rdsOut), "broadcast_fm_set_rds")) gpu::ok(sdrgpu_block_reset(_h.h), "wfm_reset");
+        base_type::tempStart();
+    }
     void reset() {
         std::lock_guard<std::recursive_mutex> lck(base_type::ctrlMtx);
         base_type::tempStop();
@@ -115,7 +125,8 @@ protected:
     }
     void rebuild() {
         sdrgpu_block* h = nullptr;
-        if (_stereo || _rdsOut) {
+        _full = _stereo || _rdsOut;
+        if (_full) {
             gpu::ok(sdrgpu_broadcast_fm_create(&h, _h.bind(gpu::device()), _deviation, _samplerate, _stereo, _lowPass), "broadcast_fm_create");
             if (h && _rdsOut) gpu::ok(sdrgpu_broadcast_fm_set_rds(h, 1), "broadcast_fm_set_rds");
         } else {
@@ -125,6 +136,7 @@ protected:
     }
     double _deviation = 0, _samplerate = 0;
     bool _stereo = false, _lowPass = true, _rdsOut = false;
+    bool _full = false;   // _h is a sdrgpu_broadcast_fm handle (stereo decoder and RDS branch), not the mono one
     gpu::Handle _h;
 };
 }  // namespace dsp::demod

@@ -397,5 +397,13 @@ def test_reset_reproduces_the_first_run(name):
     run = lambda: np.concatenate([b.process(X[:480]), b.process(X[480:])])   # (squelch: a loud call, then a quiet one)
     first = run()
     b.reset()
-    assert same(run(), first)
+    if name == "am":
+        # AM::reset() (am.h:104-112) resets the AGCs and the DC blocker and leaves the low-pass filter's history, as
+        # tests/test_ref_demod.py pins to the reference: the run after it agrees with the first one from the row on
+        # at which the filter holds this run's rows only, and not before
+        H = len(dsp.low_pass(AM_ARGS[0] / 2.0, (AM_ARGS[0] / 2.0) * 0.1, FS)) - 1
+        again = run()
+        assert 0 < H < 480 and same(again[H:], first[H:]) and not same(again[:H], first[:H])
+    else:
+        assert same(run(), first)
     assert not same(run(), first), "the state does not matter here: the check would show nothing"

@@ -12,7 +12,11 @@ tree) checks against them.
   FrequencyXlator, FIR / DecimatingFIR, PowerDecimator, the resamplers, RxVFO, Quadrature, FM and the
   literal DDC chains with their setters and resets: ref_chain_*.npz, one file per case (two where the
   arrays would exceed the size limit). `chain_fixtures()` builds them; tests/test_ref_chain.py holds
-  the C oracle and the device blocks to them and requires that a fresh build reproduces them."""
+  the C oracle and the device blocks to them and requires that a fresh build reproduces them.
+* the same probe's analogue-demodulator modes (and ref_blocks_trig64, cosf / sinf / atan2f evaluated in fp64) --
+  demod::AM, SSB, CW and BroadcastFM with their setters and reset: ref_demod_*.npz, one file per case.
+  `demod_fixtures()` builds them; tests/test_ref_demod.py holds the C oracle, the device blocks and the
+  banks to them and requires that a fresh build reproduces them."""
 import hashlib
 import os
 import subprocess
@@ -359,6 +363,200 @@ def chain_fixtures():
     return files
 
 
+# ---------------------------------------------------------------- analogue demodulators (ref_demod_*.npz)
+DEMOD_FS = {"am": 48000.0, "ssb": 24000.0, "cw": 24000.0, "bfm": 240000.0}
+BFM_DELAY = 153                          # ((305 - 1) / 2) + 1 at 240 kS/s: lprDelay / lmrDelay (broadcast_fm.h:47-48)
+MOVED_WINDOW = 2000                      # outputs after a setter over which `moved` is taken
+
+
+def to_i16(x):
+    x = np.asarray(x)
+    return np.round(np.stack([x.real, x.imag], 1) * 32768).clip(-32768, 32767).astype(np.int16)
+
+
+def am_input_i16(n=12000):
+    """test_am_vs_oracle's carrier (700 Hz at 60 % on a 300 Hz offset) at 0.0125, noise of 0.00025, samples
+    3500..4000 scaled x40 (the burst that fires the clip look-ahead) and 5200..5900 exact zeros (the silent gap)."""
+    fs, t, rng = DEMOD_FS["am"], np.arange(n), np.random.default_rng(0xA11)
+    x = 0.0125 * (1.0 + 0.6 * np.sin(2 * np.pi * 700 * t / fs)) * np.exp(1j * (2 * np.pi * 300 * t / fs + 0.3))
+    x = x + 0.00025 * (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n))
+    x[3500:4000] *= 40
+    x[5200:5900] = 0
+    return to_i16(x)
+
+
+def ssb_input_i16(n=8000):
+    """test_ssb_vs_oracle's two tones (1100 Hz, -700 Hz) at 0.05 and 0.0125, noise of 0.0005, samples 2000..2100 x15."""
+    fs, t, rng = DEMOD_FS["ssb"], np.arange(n), np.random.default_rng(0x55B)
+    x = 0.05 * np.exp(2j * np.pi * 1100 * t / fs) + 0.0125 * np.exp(-2j * np.pi * 700 * t / fs)
+    x = x + 0.0005 * (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n))
+    x[2000:2100] *= 15
+    return to_i16(x)
+
+
+def cw_input_i16(n=8000):
+    """test_bank_ssb.py's keyed tone (300 Hz, on and off every 2400 samples) at 0.12, noise of 0.0012, samples
+    10..2000 at 0.9: above the AGC's initial running amplitude of 1 / gain, so the look-ahead fires."""
+    fs, t, rng = DEMOD_FS["cw"], np.arange(n), np.random.default_rng(0xC3)
+    amp = np.where((t // 2400) % 2 == 0, 0.12, 0.0)
+    amp[10:2000] = 0.9
+    x = amp * np.exp(1j * (2 * np.pi * 300 * t / fs))
+    x = x + 0.0012 * (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n))
+    return to_i16(x)
+
+
+def fm_stereo_iq(n, fs, left_hz=1000.0, right_hz=0.0, seed=3, carrier=np.cos):
+    """tests/test_loops.py's fm_stereo_iq: mpx = 0.45 (L+R) + 0.45 (L-R) cos(2 th) + 0.1 cos(th), 75 kHz deviation.
+    carrier=np.sin: pilot sin(th) and subcarrier sin(2 th), the phase relation of the broadcast standard (the
+    subcarrier crosses zero upwards where the pilot does), which is the one the reference's decoder separates."""
+    t = np.arange(n) / fs
+    L = np.sin(2 * np.pi * left_hz * t) if left_hz else np.zeros(n)
+    R = np.sin(2 * np.pi * right_hz * t) if right_hz else np.zeros(n)
+    th = 2 * np.pi * 19000 * t
+    mpx = 0.45 * (L + R) + 0.45 * (L - R) * carrier(2 * th) + 0.1 * carrier(th)
+    ph = 2 * np.pi * 75000 * np.cumsum(mpx) / fs
+    rng = np.random.default_rng(seed)
+    return (0.5 * np.exp(1j * ph) + 1e-3 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))).astype(np.complex64)
+
+
+def demod_cases():
+    """name -> (mode, params, int16 input, op list, small, output dtype, builds): every analogue-demodulator case.
+    Each op of a list is one that acts in that case: setAGCGain only where the AGC is off (an enabled AGC overwrites
+    the gain at the next sample, agc.h), attack / decay only where it is on."""
+    f32, c64 = np.float32, np.complex64
+    C = {}
+    fs = DEMOD_FS["am"]
+    am = lambda m: [m, 10000.0, 50.0 / fs, 5.0 / fs, 10.0 / fs, fs]
+    on = [3001, "a0.004x0.0005", 2000, "b0.002", 2000, "r", 4999]      # the reset at 7001: the carrier fills the low-pass
+    xi = am_input_i16()
+    C["am_carrier"] = ("am_f", am(1), xi, on, 20, f32, ("", "_sum4"))
+    C["am_audio"] = ("am_f", am(2), xi, on, 20, f32, ("", "_sum4"))
+    C["am_off"] = ("am_f", am(0), xi, ["g3.5", 3001, "g30", 2000, "b0.002", 2000, "r", 1500, "g3.5", 3499], 20, f32, ("", "_sum4"))
+    C["am_stereo"] = ("am_s", am(2), xi, on, 20, c64, ("", "_sum4"))
+    C["am_reset"] = ("am_f", am(2), xi, [5001, "r", 6999], 20, f32, ("", "_sum4"))   # the reset alone: every op a bank has
+    fs = DEMOD_FS["ssb"]
+    ssb = lambda m, agc: [m, 2800.0, fs, agc, 50.0 / fs, 5.0 / fs]
+    ops = [3001, "a0.01x0.001", 1500, "e0", 1000, "g2", 1000, "e1", 1499]
+    xi = ssb_input_i16()
+    rot = ("", "_sum4", "_rot64")
+    C["ssb_usb"] = ("ssb_f", ssb(0, 1), xi, ops, 5, f32, rot)
+    C["ssb_lsb"] = ("ssb_f", ssb(1, 1), xi, ops, 5, f32, rot)
+    C["ssb_dsb"] = ("ssb_f", ssb(2, 1), xi, ops, 5, f32, rot)
+    C["ssb_stereo"] = ("ssb_s", ssb(0, 1), xi, ops, 5, c64, rot)
+    C["ssb_agc_off"] = ("ssb_f", ssb(0, 0), xi, [4001, 3999], 5, f32, rot)          # the 1e7 limiter throughout
+    cw = lambda agc: [800.0, agc, 50.0 / fs, 5.0 / fs, fs]
+    ops = [3001, "w700", 1500, "e0", 1000, "g0.5", 1000, "e1", 1499]
+    xi = cw_input_i16()
+    C["cw"] = ("cw_f", cw(1), xi, ops, 5, f32, rot)
+    C["cw_stereo"] = ("cw_s", cw(1), xi, ops, 5, c64, rot)
+    # CW's AGC starts at gain 1 (cw.h:20): the radio module's gain makes the disabled branch the limiter at clip 1
+    C["cw_agc_off"] = ("cw_f", cw(0), xi, ["g1e7", 4001, "w700", 3999], 5, f32, rot)
+    fs = DEMOD_FS["bfm"]
+    xi = to_i16(fm_stereo_iq(24000, fs))
+    bfm = lambda st, lp, rds: [100000.0, fs, st, lp, rds]
+    trig = ("", "_sum4", "_trig64")
+    C["bfm_stereo_lp"] = ("bfm", bfm(1, 1, 0), xi, [12001, 11999], 20, c64, trig)
+    C["bfm_stereo_std"] = ("bfm", bfm(1, 1, 0), to_i16(fm_stereo_iq(24000, fs, carrier=np.sin)), [12001, 11999], 20, c64, trig)
+    C["bfm_stereo_raw"] = ("bfm", bfm(1, 0, 0), xi, [12001, 11999], 20, c64, trig)
+    C["bfm_mono"] = ("bfm", bfm(0, 1, 0), xi, [12001, 11999], 20, c64, trig)
+    C["bfm_stereo_rds"] = ("bfm", bfm(1, 1, 1), xi, [12001, 11999], 20, c64, trig + ("_rot64",))
+    C["bfm_mono_rds"] = ("bfm", bfm(0, 1, 1), xi, [12001, 11999], 20, c64, trig + ("_rot64",))
+    C["bfm_ops"] = ("bfm", bfm(1, 1, 1), xi, [12001, "r", 4000, "R0", 4000, "R1", 3999], 20, c64, trig + ("_rot64",))
+    return C
+
+
+def demod_cut_calls(n, small, extra=()):
+    """`n` samples as calls: 1, 0, `small`, 7, 0, 129, 1024, 1025, `extra`, then what is left in two unequal calls."""
+    out = []
+    for c in (1, 0, small, 7, 0, 129, 1024, 1025) + tuple(extra):
+        if sum(out) + c > n:
+            break
+        out.append(c)
+    rest = n - sum(out)
+    return out + ([rest // 3, rest - rest // 3] if rest > 2 else [rest] if rest else [])
+
+
+def demod_run(build, mode, ops, params, x, out_dtype):
+    """One run of ref_blocks<build>: {counts, y[, z (AM: the low-pass input)][, rds_counts, rds (bfm)]}."""
+    raw = subprocess.run([BLOCKS + build, mode, ops, *map(num, params)], input=x.tobytes(), capture_output=True, check=True).stdout
+    nc = int(np.frombuffer(raw[:4], np.int32)[0])
+    counts = np.frombuffer(raw[4:4 + 4 * nc], np.int32)
+    total, at = int(counts.sum()), 4 + 4 * nc
+    r = {"counts": counts, "y": np.frombuffer(raw[at:at + total * np.dtype(out_dtype).itemsize], out_dtype)}
+    rest = raw[at + r["y"].nbytes:]
+    if mode.startswith("am_"):
+        r["z"] = np.frombuffer(rest, np.float32)
+        assert len(r["z"]) == total
+    elif mode == "bfm":
+        r["rds_counts"] = np.frombuffer(rest[:4 * nc], np.int32)
+        r["rds"] = np.frombuffer(rest[4 * nc:], np.complex64)
+        assert len(r["rds"]) == int(r["rds_counts"].sum())
+    else:
+        assert not rest
+    return r
+
+
+def max_gap(a, b):
+    if a.shape != b.shape:
+        return float("inf")
+    if not a.size:
+        return 0.0
+    a, b = a.view(np.float32).astype(np.float64), b.view(np.float32).astype(np.float64)
+    return float(np.abs(a - b).max())
+
+
+def demod_fixtures():
+    """{file name: {key: array}} of every ref_demod_*.npz: per case the int16 input, parameters, both op lists and,
+    per feed, the ascending build's per-call counts, outputs and tail streams. Of the other builds the counts and
+    `gap_<stream><build>`, the largest distance of that build's stream from the ascending build's in that feed
+    ([whole, cut]), are kept: the outputs themselves would take the files past the size limit. `clipped` is the
+    smallest share over builds and feeds of outputs at the AGC's clip (the AGC-off cases), `op_at` / `moved` the
+    output index of every mid-stream op of the whole feed and how far the MOVED_WINDOW outputs after it lie from a
+    run of the same case without that op."""
+    files = {}
+    for name, (mode, params, xi, segs, small, dt, builds) in demod_cases().items():
+        x = from_i16(xi)
+        assert sum(s for s in segs if not isinstance(s, str)) == len(x), name
+        extra = (BFM_DELAY - 1, BFM_DELAY, BFM_DELAY + 1) if mode == "bfm" else ()
+        g = {"mode": np.array(mode), "params": np.array(params, np.float64), "xi16": xi, "builds": np.array(builds[1:])}
+        feeds = {"whole": ",".join(map(str, segs)),
+                 "cut": ",".join(s if isinstance(s, str) else ",".join(map(str, demod_cut_calls(s, small, extra))) for s in segs)}
+        streams = ["y"] + (["z"] if mode.startswith("am_") else []) + (["rds"] if mode == "bfm" else [])
+        gaps = {(st, b): [] for st in streams for b in builds[1:]}
+        clip, clipped = (10.0 if mode.startswith("ssb") else 1.0), []
+        for feed, ops in feeds.items():
+            g[f"ops_{feed}"] = np.array(ops)
+            base = demod_run("", mode, ops, params, x, dt)
+            for k, v in base.items():
+                g[f"{feed}_{k}"] = v
+            clipped.append(float(np.mean(np.abs(base["y"].view(np.float32)) >= clip * (1 - 1e-6))))
+            for b in builds[1:]:
+                r = demod_run(b, mode, ops, params, x, dt)
+                g[f"{feed}_counts{b}"] = r["counts"]
+                if mode == "bfm":
+                    g[f"{feed}_rds_counts{b}"] = r["rds_counts"]
+                for st in streams:
+                    gaps[(st, b)].append(max_gap(base[st], r[st]))
+                clipped.append(float(np.mean(np.abs(r["y"].view(np.float32)) >= clip * (1 - 1e-6))))
+        for (st, b), v in gaps.items():
+            g[f"gap_{st}{b}"] = np.array(v)
+        if name.endswith("_agc_off"):
+            g["clipped"] = np.array(min(clipped))
+        # every mid-stream op of the whole feed: the same case without it
+        op_at, moved, done = [], [], 0
+        for k, s in enumerate(segs):
+            if not isinstance(s, str):
+                done += s
+                continue
+            without = demod_run("", mode, ",".join(map(str, segs[:k] + segs[k + 1:])), params, x, dt)["y"]
+            a, b = g["whole_y"][done:done + MOVED_WINDOW], without[done:done + MOVED_WINDOW]
+            op_at.append(done)
+            moved.append(max_gap(a, b))
+        g["op_at"], g["moved"] = np.array(op_at, np.int64), np.array(moved)
+        files[f"ref_demod_{name}.npz"] = g
+    return files
+
+
 # Known-answer signals of the chain fixtures: the seed of shaped_psk / gfsk_signal, (f0, snr_db, seed) of
 # rds_signal. tests/test_ref_blocks.py test_chain_inputs_meet_the_preconditions states the conditions they
 # are chosen to meet (both builds decide alike, no symbol within the comparison bar of a decision boundary,
@@ -394,7 +592,7 @@ def main():
     offs = np.array([2 * np.pi * (-1.5e6 / 61.44e6), 2 * np.pi * (-2.5e6 / 61.44e6), 2 * np.pi * (2.5e6 / 61.44e6)])
     deltas = np.stack([np.frombuffer(probe("xlatordelta", f"{float(o):.17g}"), np.float32) for o in offs])
     np.savez_compressed(os.path.join(OUT, "ref_quad.npz"), x=x, dev=dev, y=y, offs=offs, deltas=deltas)
-    for fname, arrays in {**blocks_fixtures(), **chain_fixtures()}.items():
+    for fname, arrays in {**blocks_fixtures(), **chain_fixtures(), **demod_fixtures()}.items():
         path = os.path.join(OUT, fname)
         np.savez_compressed(path, **arrays)
         size = os.path.getsize(path)
