@@ -53,6 +53,13 @@
 //   ssb_f|ssb_s  mode bandwidth samplerate agcEnabled attack decay       demod::SSB<float|stereo_t>
 //   cw_f|cw_s  tone agcEnabled attack decay samplerate                   demod::CW<float|stereo_t>
 //   bfm  deviation samplerate stereo lowPass rdsOut                      demod::BroadcastFM
+// Carrier loops and the Meteor demodulator (the decoder module's header, on the include path). Ops: `r` reset() (all
+// four), `b<0|1>` setBrokenModulation() (mcostas, meteor: the letter's meaning is per mode, as `w`'s is),
+// `q<0|1>` Meteor::setOQPSK().
+//   pll|cpll  bandwidth initPhase initFreq minFreq maxFreq               loop::PLL | loop::CarrierTrackingPLL
+//   mcostas  bandwidth broken initPhase initFreq minFreq maxFreq         loop::MeteorCostas
+//   meteor  symbolrate samplerate rrcTaps rrcBeta agcRate costasBw broken oqpsk omegaGain muGain omegaRelLimit
+//                                                                        demod::Meteor
 // Design code (no stdin, <calls> ignored; stdout float32 only):
 //   rrc  count beta Ts                                      taps::rootRaisedCosine<float>
 //   mmbank  P T                                             the bank MM builds for itself, [P][T]
@@ -94,13 +101,16 @@
 #include <dsp/demod/ssb.h>
 #include <dsp/demod/cw.h>
 #include <dsp/demod/broadcast_fm.h>
+#include <dsp/loop/pll.h>
+#include <dsp/loop/carrier_tracking_pll.h>
+#include "meteor_demod.h"
 
 using dsp::complex_t;
 using dsp::stereo_t;
 
 struct Op {
     char kind;      // 'p' process, 'r' reset, 'o' setOmega, 'i' setInterpParams, 'w' 'f' 'd' 't' 'v' the chain's setters,
-                    // 'g' 'e' 'a' 'b' 'R' the demodulators'
+                    // 'g' 'e' 'a' 'b' 'R' 'q' the demodulators'
     int count = 0, a = 0, b = 0;
     double v = 0.0, v2 = 0.0;
 };
@@ -122,7 +132,7 @@ static std::vector<Op> parseCalls(const char* s) {
         else if (tok[0] == 'w' || tok[0] == 'f' || tok[0] == 'v') { op.kind = tok[0]; op.v = strtod(tok.c_str() + 1, NULL); }
         else if (tok[0] == 'g' || tok[0] == 'b') { op.kind = tok[0]; op.v = strtod(tok.c_str() + 1, NULL); }
         else if (tok[0] == 'a') { op.kind = 'a'; sscanf(tok.c_str() + 1, "%lfx%lf", &op.v, &op.v2); }
-        else if (tok[0] == 'e' || tok[0] == 'R') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
+        else if (tok[0] == 'e' || tok[0] == 'R' || tok[0] == 'q') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
         else if (tok[0] == 'd' || tok[0] == 't') { op.kind = tok[0]; op.a = atoi(tok.c_str() + 1); }
         else { op.kind = 'p'; op.count = atoi(tok.c_str()); }
         ops.push_back(op);
@@ -497,6 +507,15 @@ static int runBFM(const std::vector<Op>& ops, char** p) {
     });
 }
 
+// ------------------------------------------------------------------ carrier loops, Meteor
+template <class B>
+static int runPLL(const std::vector<Op>& ops, char** p) {
+    auto& b = zeroed<B>();
+    b.init(NULL, atof(p[0]), atof(p[1]), atof(p[2]), atof(p[3]), atof(p[4]));
+    return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); },
+                                          [&](const Op& op) { if (op.kind == 'r') { b.reset(); } else { badOp(op); } });
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) { return 2; }
     std::string mode = argv[1];
@@ -603,6 +622,31 @@ int main(int argc, char** argv) {
     if (mode == "cw_f" && np == 5) { return runCW<float>(ops, p); }
     if (mode == "cw_s" && np == 5) { return runCW<stereo_t>(ops, p); }
     if (mode == "bfm" && np == 5) { return runBFM(ops, p); }
+
+    if (mode == "pll" && np == 5) { return runPLL<dsp::loop::PLL>(ops, p); }
+    if (mode == "cpll" && np == 5) { return runPLL<dsp::loop::CarrierTrackingPLL>(ops, p); }
+    if (mode == "mcostas" && np == 6) {
+        auto& b = zeroed<dsp::loop::MeteorCostas>();
+        b.init(NULL, atof(p[0]), atoi(p[1]) != 0, atof(p[2]), atof(p[3]), atof(p[4]), atof(p[5]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); },
+                                              [&](const Op& op) {
+            if (op.kind == 'r') { b.reset(); }
+            else if (op.kind == 'b') { b.setBrokenModulation(op.v != 0); }
+            else { badOp(op); }
+        });
+    }
+    if (mode == "meteor" && np == 11) {
+        auto& b = zeroed<dsp::demod::Meteor>();
+        b.init(NULL, atof(p[0]), atof(p[1]), atoi(p[2]), atof(p[3]), atof(p[4]), atof(p[5]), atoi(p[6]) != 0, atoi(p[7]) != 0,
+               atof(p[8]), atof(p[9]), atof(p[10]));
+        return runCalls<complex_t, complex_t>(ops, [&](int n, complex_t* in, complex_t* out) { return b.process(n, in, out); },
+                                              [&](const Op& op) {
+            if (op.kind == 'r') { b.reset(); }
+            else if (op.kind == 'b') { b.setBrokenModulation(op.v != 0); }
+            else if (op.kind == 'q') { b.setOQPSK(op.a != 0); }
+            else { badOp(op); }
+        });
+    }
 
     if (mode == "rrc" && np == 3) {
         dsp::tap<float> t = dsp::taps::rootRaisedCosine<float>(atoi(p[0]), atof(p[1]), atof(p[2]));

@@ -90,11 +90,11 @@ def build_lib(force=False, variant=None, defines=()):
 
 def build_oracle():
     """The checker (test infrastructure): the C restatement, and -- where the reference tree is
-    mounted (dev container only) -- oracle/_ref/ref_probe built from the reference's own headers."""
+    mounted (dev container only) -- the oracle/_ref probes built from the reference's own headers
+    (oracle/Makefile's `ref` builds nothing where the tree is absent)."""
     odir = os.path.join(ROOT, "oracle")
     _run(["make", "-C", odir, "-s"])
-    if os.path.isdir("/root/reference/core/src/dsp"):
-        _run(["make", "-C", odir, "-s", "ref"])
+    _run(["make", "-C", odir, "-s", "ref"])
     return os.path.join(odir, "libsdr_oracle.so")
 
 

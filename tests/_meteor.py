@@ -7,7 +7,7 @@ and RefMM. The per-sample loops carry a leading batch axis (one independent stre
 `trig`: cs(p) -> (cosf, sinf) and atan2(y, x) -> atan2f, in numpy's float32 (trig32) or in fp64 rounded once
 (trig64); the gap between the two runs is the loop's own sensitivity to the last bit of its libm.
 tests/test_meteor_ref.py holds these functions to the reference's own code (tests/golden/ref_meteor_*.npz, made
-by tools/gen_meteor_fixtures.py); the device tests hold the kernels to these functions."""
+by tools/gen_ref_fixtures.py meteor_fixtures); the device tests hold the kernels to these functions."""
 import functools
 from types import SimpleNamespace
 
@@ -230,7 +230,7 @@ def bank_carriers(S, n=N, seed0=400):
                                           for k in range(S)], 1))
 
 
-# ------------------------------------------------- the fixture cases (tools/gen_meteor_fixtures.py)
+# ------------------------------------------------- the fixture cases (tools/gen_ref_fixtures.py meteor_fixtures)
 # The loops alone. PLL and CarrierTrackingPLL track a noisy carrier at 0.05 rad/sample; MeteorCostas takes the LRPT
 # signals at unit rms (what the AGC hands it). 8 seeds per case: S is over all of them, seed [0] is the fixture's.
 LOOP_BW = 0.01                                                  # PLL / CarrierTrackingPLL bandwidth
@@ -254,7 +254,7 @@ def unit_lrpt(seed, kind):
     return (lrpt_signal(seed, kind)[0] / f32(0.05)).astype(np.complex64)
 
 
-# Seeds of the demodulator cases, found by tools/gen_meteor_fixtures.py --search. MM decides an interpolator phase
+# Seeds of the demodulator cases, found by tools/gen_ref_fixtures.py --meteor-search. MM decides an interpolator phase
 # per symbol, floor(u) of u = phase * 128 (mm.h:111), and with it the offset. The phase before the floor is
 # ~2.08 + a fraction, so u moves in steps of 128 ulp(2.08) = 3.05e-5, and the rounding of every step walks it by a
 # few such steps between two runs that differ in the last bit of the loop's libm (S_u of the two restatements:

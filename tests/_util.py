@@ -199,3 +199,39 @@ def two_pass_fft(N, nz, window=6):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+_generator = []
+
+
+def ref_generator():
+    """tools/gen_ref_fixtures.py as a module (loaded once)."""
+    if not _generator:
+        import importlib.util
+        path = os.path.join(os.path.dirname(GOLDEN), "..", "tools", "gen_ref_fixtures.py")
+        spec = importlib.util.spec_from_file_location("gen_ref_fixtures", path)
+        _generator.append(importlib.util.module_from_spec(spec))
+        spec.loader.exec_module(_generator[0])
+    return _generator[0]
+
+
+def have_reference():
+    """The one skip condition of the live-probe tests: the reference's dsp headers and the Meteor module's."""
+    return ref_generator().have_reference()
+
+
+def assert_live_probe_reproduces(prefix, fixtures):
+    """A fresh build of the reference probes reproduces every committed tests/golden/<prefix>*.npz: the same files,
+    the same keys, and per array the same dtype, shape and bytes. `fixtures` names the generator's function."""
+    import subprocess
+    gen = ref_generator()
+    subprocess.check_call(["make", "-C", os.path.join(gen.ROOT, "oracle"), "-s", "ref"])
+    files = getattr(gen, fixtures)()
+    assert sorted(files) == sorted(f for f in os.listdir(GOLDEN) if f.startswith(prefix))
+    for fname, arrays in files.items():
+        assert os.path.getsize(os.path.join(GOLDEN, fname)) <= gen.MAX_BYTES, fname
+        g = np.load(os.path.join(GOLDEN, fname))
+        assert sorted(g.files) == sorted(arrays), fname
+        for k, v in arrays.items():
+            v = np.asarray(v)
+            assert g[k].dtype == v.dtype and g[k].shape == v.shape and g[k].tobytes() == v.tobytes(), f"{fname}: {k}"

@@ -1,6 +1,6 @@
 """The Meteor demodulator and the carrier loops against the REFERENCE's own code: tests/golden/ref_meteor_*.npz hold
 what loop::PLL, loop::CarrierTrackingPLL, loop::MeteorCostas and demod::Meteor compute, run from the reference's headers
-by tools/ref_meteor_probe.cpp (tools/gen_meteor_fixtures.py).
+by oracle/ref_blocks.cpp's pll, cpll, mcostas and meteor modes (tools/gen_ref_fixtures.py meteor_fixtures).
 
 CPU: every restatement of tests/_meteor.py reproduces the fixtures -- whole calls and cuts (the generator asserts that
 the reference gives the same outputs either way and keeps them once; the demodulator's per-call counts are kept for
@@ -17,19 +17,17 @@ every decision of MM, the fixture's stream being the one whose decisions stay fa
 MM_MARGIN); that precondition, and that the bar stays under 1 % of the constellation radius, are asserted on the
 restatements alone. Recorded through write_report: meteor_parity."""
 import os
-import tempfile
 
 import numpy as np
 import pytest
 
 import sdrpp_amd
 from sdrpp_amd import dsp
-from _util import GOLDEN, write_report
+from _util import GOLDEN, assert_live_probe_reproduces, have_reference, write_report
 from _restated import N, CUTS, FL_M_PI, same, parts, ref_costas
 import _meteor as M
 
 RADIUS = 1.0                                                     # the AGC's set point (meteor_demod.h:33)
-HAVE_REF = os.path.isdir("/root/reference/core/src/dsp")
 PI = float(FL_M_PI)
 gpu = pytest.mark.gpu
 
@@ -137,21 +135,9 @@ def test_meteor_restatement_reproduces_the_reference(name):
         held(f"meteor {name} {kind}", r[kind], want, r["bar"], r["S"], "restatement")
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not mounted (dev container only)")
+@pytest.mark.skipif(not have_reference(), reason="reference tree not mounted (GPU box): the committed fixtures cover it")
 def test_a_fresh_probe_build_reproduces_the_committed_fixtures():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), "..", "tools"))
-    import gen_meteor_fixtures as G
-    with tempfile.TemporaryDirectory() as tmp:
-        files = G.fixtures(G.build_probe(tmp))
-    assert sorted(files) == sorted(f for f in os.listdir(GOLDEN) if f.startswith("ref_meteor_"))
-    for fname, arrays in files.items():
-        g = np.load(os.path.join(GOLDEN, fname))
-        assert sorted(g.files) == sorted(arrays), fname
-        for k, v in arrays.items():
-            v = np.asarray(v)
-            assert g[k].dtype == v.dtype and g[k].shape == v.shape and g[k].tobytes() == v.tobytes(), f"{fname}: {k}"
-        assert os.path.getsize(os.path.join(GOLDEN, fname)) <= G.MAX_BYTES
+    assert_live_probe_reproduces("ref_meteor_", "meteor_fixtures")
 
 
 # ------------------------------------------------------------------ gpu: the device blocks

@@ -45,7 +45,6 @@ Bars:
   (tests/_restated.py SquelchRef); the fixture runs a single object, so the two cannot differ.
 Recorded: profiles/r12/ref_pin.json.
 """
-import importlib.util
 import os
 
 import numpy as np
@@ -54,11 +53,10 @@ import pytest
 import oracle
 import sdrpp_amd
 from sdrpp_amd import dsp
-from _util import EPS32, GOLDEN, write_report
+from _util import EPS32, GOLDEN, assert_live_probe_reproduces, have_reference, write_report
 import _restated as R
 from _restated import f32, N, CUTS, same, parts
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
 OM2 = 5000.0 / 1187.5
 MM_BASE = (4.0, 2.5e-5, 0.01, 0.01)
@@ -512,20 +510,6 @@ def test_chain_device_against_the_reference(name):
 
 
 # --------------------------------------------------------------- live probe
-@pytest.mark.skipif(not os.path.exists("/root/reference/core/src/dsp/clock_recovery/mm.h"),
-                    reason="reference tree not mounted (GPU box): the committed fixtures cover it")
+@pytest.mark.skipif(not have_reference(), reason="reference tree not mounted (GPU box): the committed fixtures cover it")
 def test_live_reference_probe_reproduces_the_fixtures():
-    import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
-    spec = importlib.util.spec_from_file_location("gen_ref_fixtures", os.path.join(ROOT, "tools", "gen_ref_fixtures.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    files = gen.blocks_fixtures()
-    on_disk = sorted(f for f in os.listdir(GOLDEN) if f.startswith("ref_blocks_"))
-    assert sorted(files) == on_disk
-    for fname, arrays in files.items():
-        g = np.load(os.path.join(GOLDEN, fname))
-        assert sorted(g.files) == sorted(arrays), fname
-        for k, v in arrays.items():
-            v = np.asarray(v)
-            assert g[k].dtype == v.dtype and g[k].shape == v.shape and g[k].tobytes() == v.tobytes(), f"{fname}: {k}"
+    assert_live_probe_reproduces("ref_blocks_", "blocks_fixtures")

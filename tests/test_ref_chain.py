@@ -35,7 +35,6 @@ calls of 1,200,000, 307,200 and 999 samples with set_offset and reset between th
 Recorded: profiles/r19/ref_pin_chain.json.
 """
 import glob
-import importlib.util
 import os
 
 import numpy as np
@@ -43,9 +42,8 @@ import pytest
 
 import oracle
 from sdrpp_amd import dsp
-from _util import EPS32, GOLDEN, assert_close_c, fir_atol, iq, write_report
+from _util import EPS32, GOLDEN, assert_close_c, assert_live_probe_reproduces, fir_atol, have_reference, iq, write_report
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
 FEEDS = ("whole", "cut")
 ATAN_BAR = 8 * float(np.spacing(np.float32(np.pi)))
@@ -390,20 +388,6 @@ def test_fir_walk_at_200k_per_segment_vs_oracle():
 
 
 # --------------------------------------------------------------- live probe
-@pytest.mark.skipif(not os.path.exists("/root/reference/core/src/dsp/channel/rx_vfo.h"),
-                    reason="reference tree not mounted (GPU box): the committed fixtures cover it")
+@pytest.mark.skipif(not have_reference(), reason="reference tree not mounted (GPU box): the committed fixtures cover it")
 def test_live_reference_probe_reproduces_the_fixtures():
-    import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
-    spec = importlib.util.spec_from_file_location("gen_ref_fixtures", os.path.join(ROOT, "tools", "gen_ref_fixtures.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    files = gen.chain_fixtures()
-    assert sorted(files) == sorted(f for f in os.listdir(GOLDEN) if f.startswith("ref_chain_"))
-    for fname, arrays in files.items():
-        assert os.path.getsize(os.path.join(GOLDEN, fname)) <= gen.MAX_BYTES, fname
-        g = np.load(os.path.join(GOLDEN, fname))
-        assert sorted(g.files) == sorted(arrays), fname
-        for k, v in arrays.items():
-            v = np.asarray(v)
-            assert g[k].dtype == v.dtype and g[k].shape == v.shape and g[k].tobytes() == v.tobytes(), f"{fname}: {k}"
+    assert_live_probe_reproduces("ref_chain_", "chain_fixtures")

@@ -43,7 +43,6 @@ Re(x p p) = Re(x conj(p) conj(p)) for real x, operation by operation, so the res
 Recorded: profiles/r22/ref_pin_demod.json.
 """
 import glob
-import importlib.util
 import os
 
 import numpy as np
@@ -51,9 +50,8 @@ import pytest
 
 import oracle
 from sdrpp_amd import dsp
-from _util import EPS32, GOLDEN, write_report
+from _util import EPS32, GOLDEN, assert_live_probe_reproduces, have_reference, write_report
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 gpu = pytest.mark.gpu
 FEEDS = ("whole", "cut")
 ATAN_BAR = 8 * float(np.spacing(np.float32(np.pi)))
@@ -497,20 +495,6 @@ def test_broadcast_fm_stereo_one_call_of_40000_vs_oracle():
 
 
 # --------------------------------------------------------------- live probe
-@pytest.mark.skipif(not os.path.exists("/root/reference/core/src/dsp/demod/broadcast_fm.h"),
-                    reason="reference tree not mounted (GPU box): the committed fixtures cover it")
+@pytest.mark.skipif(not have_reference(), reason="reference tree not mounted (GPU box): the committed fixtures cover it")
 def test_live_reference_probe_reproduces_the_fixtures():
-    import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref"])
-    spec = importlib.util.spec_from_file_location("gen_ref_fixtures", os.path.join(ROOT, "tools", "gen_ref_fixtures.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    files = gen.demod_fixtures()
-    assert sorted(files) == sorted(f for f in os.listdir(GOLDEN) if f.startswith("ref_demod_"))
-    for fname, arrays in files.items():
-        assert os.path.getsize(os.path.join(GOLDEN, fname)) <= gen.MAX_BYTES, fname
-        g = np.load(os.path.join(GOLDEN, fname))
-        assert sorted(g.files) == sorted(arrays), fname
-        for k, v in arrays.items():
-            v = np.asarray(v)
-            assert g[k].dtype == v.dtype and g[k].shape == v.shape and g[k].tobytes() == v.tobytes(), f"{fname}: {k}"
+    assert_live_probe_reproduces("ref_demod_", "demod_fixtures")
